@@ -11,7 +11,10 @@ Node (a fair coin picks a link batch = all edges of one vertex, or a non-link ba
 one vertex).  A step is one Learner iteration: mini-batch + neighbour sampling, update_phi, update_pi,
 the beta gradient and the theta/beta update.  With N > 1 the same problem is sharded (strong scaling).
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).  A plain run sets up, settles, warms up, times
+--steps steps and prints the line; --full adds what takes runs of its own (CPU baseline, the reference's default
+work-groups, the other configurations, the C++ drop-in, the sustained window, perplexity latency, the shader clock under
+load, the multi-GPU step trace).  --dump-outputs DIR writes the model state the timed steps left behind (dump_outputs).
 """
 import argparse
 import json
@@ -54,16 +57,20 @@ def parse():
                     help="reference-exact host mini-batch sampler (rand_r) instead of the device sampler")
     ap.add_argument("--loop", default="auto", choices=["auto", "graph", "eager"],
                     help="iteration form: captured hipGraphs (auto: one rank + device sampling) or launch by launch")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (the options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the model state they left behind to DIR/<name>.npy (float32)")
     ap.add_argument("--cpp-dropin", type=int, default=1,
-                    help="also time the C++ mcmc::Learner (ammsb_main, a child process) on the same graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: also time the C++ mcmc::Learner (ammsb_main, a child process) on the same graph")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=0, help="nodes/edges in the CPU-baseline sample")
-    ap.add_argument("--ppx-calls", type=int, default=5)
+    ap.add_argument("--ppx-calls", type=int, default=5, help="--full: HeldoutPerplexity() calls timed for ppx_eval_ms")
     ap.add_argument("--extras", type=int, default=1,
-                    help="one GPU: also time the workload at the reference's default work-group sizes (32) and, for C3, "
+                    help="--full, one GPU: also time the workload at the reference's default work-group sizes (32) and, for C3, "
                          "short C1 and C2 runs (small_configs) and BASELINE's largest configuration C5 (large_configs)")
     ap.add_argument("--large", default=os.environ.get("AMMSB_BENCH_LARGE", "auto"), choices=["auto", "C5", "C5s", "none"],
-                    help="large_configs of the default run: C5 (N=10M, K=4096: ~2 min of host set-up, 164 GB of pi), its "
+                    help="large_configs of the --full run: C5 (N=10M, K=4096: ~2 min of host set-up, 164 GB of pi), its "
                          "2M-vertex stand-in C5s, none; auto = C5 when HBM and host memory allow, else C5s")
     ap.add_argument("--watchdog-s", type=float, default=-1.0,
                     help="give up (exit 124, naming the phase and the rank on stderr and, from rank 0, as a JSON line) when "
@@ -71,7 +78,7 @@ def parse():
                          "collective one rank never joins blocks its peers for RCCL's own 10 minutes and says nothing "
                          "about where), off with one; 0: off")
     ap.add_argument("--sustained-s", type=float, default=3.0,
-                    help="after the timed window: this many seconds of untimed iterations, then a SECOND window of the "
+                    help="--full: after the timed window, this many seconds of untimed iterations, then a SECOND window of the "
                          "same --steps, reported as `sustained` (what a long run sees once the package's power "
                          "controller has settled; `value` stays the contract's warm-up + steps window); 0: off")
     ap.add_argument("--settle-s", type=float, default=-8.0,
@@ -80,7 +87,10 @@ def parse():
                          "that many seconds -- the clocks' ramp from idle and, on some boxes, several seconds in which the "
                          "power controller holds a higher shader clock and the launch runs 8 %% longer are start-up, not "
                          "the measurement (profiles/README.md, round 4).  0: off")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def pick_wg(K, override, cap):
@@ -319,14 +329,18 @@ def phi_bytes_per_node(K, n):
     return 4 * K * (n + 2) + 68 * n + 8
 
 
-def measure(args, lrn, cfg, m, steps, warmup, world, dist, torch, workload, ppx_calls, settle_s=0.0):
+def measure(args, lrn, cfg, m, steps, warmup, world, dist, torch, workload, ppx_calls, settle_s=0.0, settle_lrn=None,
+            after_timed=None, clock_probe=True):
     """ppx latency, then `warmup` untimed and EXACTLY `steps` timed iterations of `lrn` (barrier + synchronize on both
-    sides, max over ranks).  Returns the numbers of one bench record."""
+    sides, max over ranks).  The settle iterations run on `settle_lrn` when given (a second Learner of the same
+    configuration: `lrn` then enters its warm-up in its initial state, whatever the settle took), else on `lrn`.
+    `after_timed()` is called right after the timed steps, before anything else runs.  Returns the numbers of one bench
+    record."""
     from mcmc_ammsb_gpu_amd import gpu_state
     K, n = cfg.K, cfg.num_node_sample
 
-    def sync():
-        lrn.drain()
+    def sync(which=lrn):
+        which.drain()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -346,27 +360,28 @@ def measure(args, lrn, cfg, m, steps, warmup, world, dist, torch, workload, ppx_
         t_s = time.perf_counter()
         hist = []
         dev_i = torch.cuda.current_device()
+        sl = settle_lrn if settle_lrn is not None else lrn
         while True:
-            first_s = lrn.phiUpdater.count_calls + 1
+            first_s = sl.phiUpdater.count_calls + 1
             if settle_s < 0:
-                lrn.step_log = []
-            lrn.Run(chunk)
-            sync()
+                sl.step_log = []
+            sl.Run(chunk)
+            sync(sl)
             settle_steps += chunk
             t_now = time.perf_counter() - t_s
             if settle_s > 0:
                 go = t_now < settle_s and settle_steps < 20000
             else:
                 phi_ms = None
-                if lrn.loop is not None:
+                if sl.loop is not None:
                     try:
-                        st_s = lrn.loop.step_stamps(first_s, chunk)
-                        non = np.concatenate(lrn.step_log) == m
+                        st_s = sl.loop.step_stamps(first_s, chunk)
+                        non = np.concatenate(sl.step_log) == m
                         if non.any():
                             phi_ms = float((st_s[non, 1] - st_s[non, 0]).mean() * 1e-6)
                     except Exception:
                         phi_ms = None
-                lrn.step_log = None
+                sl.step_log = None
                 hist.append((round(t_now, 2), phi_ms, gpu_state.read(dev_i).get("power_w")))
                 last = hist[-5:]
 
@@ -442,6 +457,8 @@ def measure(args, lrn, cfg, m, steps, warmup, world, dist, torch, workload, ppx_
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if after_timed is not None:
+        after_timed()
     edges_done = lrn.edges_done - edges_before  # identical on every rank: the whole job's mini-batch edges
     step_log = []
     for rec in lrn.step_log:
@@ -566,22 +583,23 @@ def measure(args, lrn, cfg, m, steps, warmup, world, dist, torch, workload, ppx_
     # ---- the shader clock the chip holds UNDER this workload: a few more (untimed) steps with the probe's idle waves
     # beside them on their own stream (ammsb_clock_probe) -- a roofline fraction is read against the clocks it ran at
     device_state = gpu_state.summarize(state_before, state_after)
-    try:
-        from mcmc_ammsb_gpu_amd import ops as _ops
-        probe = _ops.ClockProbe(lrn.ctx, 64)
-        n_probe = 12 if m >= 32768 else 60
-        lrn.Run(n_probe // 3)
-        probe.launch(600)
-        lrn.Run(n_probe - n_probe // 3)
-        clk = probe.read()
-        sync()
-        device_state["shader_clock_under_load_mhz"] = clk["mhz"]
-        device_state["shader_clock_per_xcd_mhz"] = clk["mhz_per_xcd"]
-        device_state["shader_clock_how"] = ("s_memtime / s_memrealtime of idle probe waves on a second stream beside %d "
-                                            "untimed steps right after the timed window" % n_probe)
-    except Exception as e:  # a measurement aid: never lose the bench line over it
-        device_state["shader_clock_under_load_mhz"] = None
-        device_state["shader_clock_how"] = "probe failed: %r" % (e,)
+    if clock_probe:  # (--full: it takes steps of its own)
+        try:
+            from mcmc_ammsb_gpu_amd import ops as _ops
+            probe = _ops.ClockProbe(lrn.ctx, 64)
+            n_probe = 12 if m >= 32768 else 60
+            lrn.Run(n_probe // 3)
+            probe.launch(600)
+            lrn.Run(n_probe - n_probe // 3)
+            clk = probe.read()
+            sync()
+            device_state["shader_clock_under_load_mhz"] = clk["mhz"]
+            device_state["shader_clock_per_xcd_mhz"] = clk["mhz_per_xcd"]
+            device_state["shader_clock_how"] = ("s_memtime / s_memrealtime of idle probe waves on a second stream beside %d "
+                                                "untimed steps right after the timed window" % n_probe)
+        except Exception as e:  # a measurement aid: never lose the bench line over it
+            device_state["shader_clock_under_load_mhz"] = None
+            device_state["shader_clock_how"] = "probe failed: %r" % (e,)
     if roofline is not None:
         roofline["device_state"] = device_state
     return {"settle_steps": settle_steps, "settle_log": settle_log, "device_state": device_state,
@@ -589,6 +607,31 @@ def measure(args, lrn, cfg, m, steps, warmup, world, dist, torch, workload, ppx_
             "host_enqueue_ms_per_step": t_enq * 1e3 / steps, "step_classes": step_classes,
             "value_per_class": value_per_class, "roofline": roofline, "ppx_ms": ppx_ms, "ppx": ppx,
             "kernel_names": names}
+
+
+def dump_outputs(lrn, out_dir):
+    """--dump-outputs: the model state the timed steps left behind, which is what a caller of Learner.Run() reads
+    afterwards, as float32 .npy files in out_dir: beta.npy and theta.npy (2K each), phi_sum.npy (the N row sums; a fixed
+    sample of 4M of them beyond that) and pi_rows.npy (a fixed sample of pi's rows, at most 32 MB, in ascending row
+    order).  The samples depend on N and K alone, so two runs with the same arguments write the same entries."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    pi = lrn.pi
+    N, K = pi.rows, pi.cols
+    rng = np.random.default_rng(20260101)
+    rows = np.sort(rng.choice(N, size=min(N, (32 << 20) // (4 * K)), replace=False))
+    parts = []
+    for b, blk in enumerate(pi.blocks):
+        sel = rows[(rows >= b * pi.rows_in_block) & (rows < (b + 1) * pi.rows_in_block)] - b * pi.rows_in_block
+        if sel.size:
+            parts.append(blk.index_select(0, torch.from_numpy(sel).to(blk.device)).cpu())
+    phi = lrn.phi.cpu().numpy()
+    if N > (4 << 20):
+        phi = phi[np.sort(rng.choice(N, size=4 << 20, replace=False))]
+    out = {"beta": lrn.beta.cpu().numpy(), "theta": lrn.theta.cpu().numpy(), "phi_sum": phi,
+           "pi_rows": torch.cat(parts).numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def sub_record(r, cfg, steps, warmup, loop):
@@ -664,6 +707,7 @@ def main():
     cfg = make_cfg(K, m, n, pick_wg(K, args.phi_wg, 16),   # K=1024 -> 64: the LDS-streamed kernel
                    pick_wg(K, args.beta_wg, 16), pick_wg(K, args.ppx_wg, 16), use_graph)
     wd.phase("Learner() incl. the split calibration's update_phi / all-gather / point-to-point timings")
+    free_before = torch.cuda.mem_get_info()[0]
     lrn = Learner(cfg, ds, rank=rank, world_size=world)
     setup_s = time.perf_counter() - t_setup
     pi_placement = getattr(lrn, "pi_placement", None)
@@ -671,14 +715,37 @@ def main():
     graphs = lrn.loop is not None
     note("learner ready (%s loop)" % ("device-descriptor" if graphs else "eager"))
 
-    r = measure(args, lrn, cfg, m, args.steps, args.warmup, world, dist, torch, args.workload, args.ppx_calls,
-                settle_s=args.settle_s)
+    # ---- the settle iterations run on a second Learner of the same configuration where the device holds two: the
+    # measured one then starts its warm-up from its initial state, so that the state after the timed steps (and what
+    # --dump-outputs writes) does not depend on how long the settle took.  With more ranks, or without the room, they run
+    # on the measured Learner.
+    settler, settle_on = None, "the measured Learner"
+    if args.settle_s != 0 and world == 1:
+        torch.cuda.empty_cache()
+        free_after = torch.cuda.mem_get_info()[0]
+        if free_after > 1.25 * (free_before - free_after) + (4 << 30):
+            t_l = time.perf_counter()
+            settler = Learner(make_cfg(K, m, n, cfg.phi_wg_size, cfg.beta_wg_size, cfg.ppx_wg_size, use_graph), ds,
+                              rank=0, world_size=1)
+            settle_on = "a second Learner of the same configuration (%.1f s to set up)" % (time.perf_counter() - t_l)
+            note("settle learner ready")
+
+    def after_timed():
+        if args.dump_outputs and rank == 0:
+            dump_outputs(lrn, args.dump_outputs)
+    r = measure(args, lrn, cfg, m, args.steps, args.warmup, world, dist, torch, args.workload,
+                args.ppx_calls if args.full else 0, settle_s=args.settle_s, settle_lrn=settler, after_timed=after_timed,
+                clock_probe=args.full)
     dt, edges_done, roofline = r["dt"], r["edges_done"], r["roofline"]
+    if settler is not None:
+        settler.close()
+        del settler
+        torch.cuda.empty_cache()
 
     # ---- the same window again after --sustained-s seconds of load: update_phi holds the package at its power cap, and
     # what the chip delivers once its power controller has settled is what a long run sees (profiles/README.md)
     sustained = None
-    if args.sustained_s > 0:
+    if args.full and args.sustained_s > 0:
         try:
             r2 = measure(args, lrn, cfg, m, args.steps, 0, world, dist, torch, args.workload, 0, settle_s=args.sustained_s)
             rf2 = r2["roofline"] or {}
@@ -695,13 +762,15 @@ def main():
             sustained = {"error": repr(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args, lrn, cfg, ds, m + 1)
         except Exception as e:  # the baseline is a reported extra; never lose the GPU number over it
             cpu = {"value": None, "unit": "mini-batch edges/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
-    wd.phase("closing HeldoutPerplexity()")
-    final_ppx = lrn.HeldoutPerplexity()
+    final_ppx = None
+    if args.full:
+        wd.phase("closing HeldoutPerplexity()")
+        final_ppx = lrn.HeldoutPerplexity()
     loop_note = loop_form(graphs)
     fallback = getattr(lrn, "loop_fallbacks", 0)
     if fallback:
@@ -710,7 +779,7 @@ def main():
                                              groups_per_block=lrn.cc, chunks=lrn.nch,
                                              beta_gradient="%s%s" % (lrn.grads_mode, " (update_pi folded into its launch)"
                                                                      if lrn.grads_mode == "replicated" and lrn.grads_fused else ""))
-    if world > 1:
+    if args.full and world > 1:
         # what makes a multi-GPU line readable by itself: a traced (untimed) window right after the timed one -- per
         # non-link step where the time went (own blocks, replicated groups, each chunk's exchange and what of it was
         # hidden, update_pi, the gradient's all-gather), next to the calibration's prediction above
@@ -738,7 +807,7 @@ def main():
 
     # ---- the same workload at the reference's DEFAULT work-group sizes (32 for phi, beta and perplexity, main.cc:61-64)
     ref_wg = None
-    if rank == 0 and world == 1 and args.extras and (cfg.phi_wg_size, cfg.beta_wg_size, cfg.ppx_wg_size) != (32, 32, 32):
+    if args.full and rank == 0 and world == 1 and args.extras and (cfg.phi_wg_size, cfg.beta_wg_size, cfg.ppx_wg_size) != (32, 32, 32):
         try:
             cfg32 = make_cfg(K, m, n, 32, 32, 32, use_graph)
             l32 = Learner(cfg32, ds, rank=0, world_size=1)
@@ -779,7 +848,7 @@ def main():
         return rec
 
     small = None
-    if rank == 0 and world == 1 and args.extras and args.workload == "C3":
+    if args.full and rank == 0 and world == 1 and args.extras and args.workload == "C3":
         small = {}
         for name, st_small in (("C1", 3000), ("C2", 2000)):
             try:
@@ -788,7 +857,7 @@ def main():
                 small[name] = {"error": repr(e)}
 
     cpp = None
-    if rank == 0 and world == 1 and args.cpp_dropin and args.workload in ("C1", "C2", "C3"):
+    if args.full and rank == 0 and world == 1 and args.cpp_dropin and args.workload in ("C1", "C2", "C3"):
         try:
             cpp = cpp_dropin(args, hostlib, N, K, m, n, cfg.phi_wg_size, edges, note)
         except Exception as e:
@@ -798,7 +867,7 @@ def main():
     # reference cannot address it: 32-bit row offsets, partitioned-alloc.h:24-28; and its perplexity kernel would
     # allocate 52 GB of scratch, perplexity.cc:245-247).  About two minutes of host set-up (graph, cuckoo sets, CSR).
     large = None
-    if rank == 0 and world == 1 and args.extras and args.workload == "C3" and args.large != "none":
+    if args.full and rank == 0 and world == 1 and args.extras and args.workload == "C3" and args.large != "none":
         del ds, edges
         import gc
         gc.collect()
@@ -865,7 +934,9 @@ def main():
             "large_configs": large,
             "sustained": sustained,
             "pi_placement": pi_placement,
+            "full": args.full,
             "settle": {"seconds": args.settle_s, "steps": r.get("settle_steps", 0), "auto": r.get("settle_log"),
+                       "on": settle_on if args.settle_s != 0 else None,
                        "why": "untimed iterations in front of the warm-up steps: the clocks' ramp from idle (a few hundred "
                               "milliseconds) is not part of the measurement; `sustained` is the window after seconds of load"},
             "cpp_dropin": cpp,

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,7 +87,7 @@ def test_plain_bench_two_ranks_end_to_end():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--workload", "C1", "--steps", "30", "--warmup", "5",
-                          "--no-cpu-baseline", "--cpp-dropin", "0", "--sustained-s", "0.5"], env=env, capture_output=True,
+                          "--no-cpu-baseline", "--cpp-dropin", "0", "--sustained-s", "0.5", "--full"], env=env, capture_output=True,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -119,7 +120,7 @@ def test_single_gpu_line_carries_device_state_and_settle():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, BENCH, "--workload", "C1", "--steps", "200", "--warmup", "20", "--settle-s", "0.2",
                           "--sustained-s", "0.3",
-                          "--no-cpu-baseline", "--cpp-dropin", "0", "--extras", "0"], env=env, capture_output=True,
+                          "--no-cpu-baseline", "--cpp-dropin", "0", "--extras", "0", "--full"], env=env, capture_output=True,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -135,3 +136,36 @@ def test_single_gpu_line_carries_device_state_and_settle():
     assert len(ds["sclk_mhz"]) == 2 and len(ds["power_w"]) == 2 and ds["power_cap_w"][0] > 0
     assert 300 < ds["shader_clock_under_load_mhz"] < 2600 and len(ds["shader_clock_per_xcd_mhz"]) == 8
     assert rec["large_configs"] is None and rec["small_configs"] is None  # (--extras 0)
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_reproduce(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries none of the extras; --dump-outputs writes the
+    model state after the timed steps as float32 .npy files, the same from run to run although the adaptive settle in
+    front of the warm-up may take a different number of iterations each time."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / ("out%d" % i))
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "C1", "--steps", "50", "--warmup", "5",
+                              "--dump-outputs", d], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 50 and rec["warmup"] == 5 and rec["value"] > 0 and rec["ms_per_step"] > 0
+        assert rec["unit"] == "edges/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert rec["full"] is False and rec["settle"]["steps"] > 0
+        for key in ("sustained", "cpu_baseline", "reference_default_wg", "small_configs", "large_configs", "cpp_dropin",
+                    "ppx_eval_ms", "perplexity_after"):
+            assert rec[key] is None, key
+        arrs = {}
+        for name in ("beta", "theta", "phi_sum", "pi_rows"):
+            a = np.load(os.path.join(d, name + ".npy"))
+            assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+            arrs[name] = a
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["pi_rows"].shape == (10_000, 32)  # C1: N = 10k rows of K = 32, all within the 32 MB sample
+        dumps.append(arrs)
+    for name in dumps[0]:
+        np.testing.assert_allclose(dumps[1][name], dumps[0][name], rtol=1e-5, atol=1e-7, err_msg=name)
