@@ -338,7 +338,8 @@ int ammsb_loop_step_stamps(ammsb_loop* loop, uint32_t first_step, uint32_t n_ste
  * context dispatched to (which = 0 / 1 / 2 / 3), spelled as the rocprofv3 kernel trace spells it (a substring of the
  * trace's name column); "" before the first call.  update_phi has two slots: launches of at most AMMSB_PHI_WIDE (512)
  * groups -- link mini-batches -- take a several-waves-per-node kernel, recorded under which = 4; which = 0 is the form
- * the large launches take. */
+ * the large launches take.  which = 5: the last ammsb_sample_neighbors call; which = 6: the partial-row sum that followed
+ * the last gradient (sum_partials8_kernel, or sum_partials_kernel when K is not a multiple of 4). */
 const char* ammsb_last_kernel_name(const ammsb_ctx* ctx, int which);
 
 /* Measurement aid (no reference counterpart): n_blocks one-wave blocks each idle for spin_us microseconds of the

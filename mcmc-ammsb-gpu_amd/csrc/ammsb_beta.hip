@@ -1508,10 +1508,13 @@ static int beta_grads_common(ammsb_ctx* ctx, const float* theta, const float* be
     AMMSB_LAUNCH_CHECK(ctx);
     return AMMSB_OK;
   }
-  if ((2 * K) % 8 == 0 && (reinterpret_cast<uintptr_t>(grads_out) & 15) == 0)
+  if ((2 * K) % 8 == 0 && (reinterpret_cast<uintptr_t>(grads_out) & 15) == 0) {
+    ctx->kernel_name[AMMSB_KN_GRADS_SUM] = "sum_partials8_kernel";
     sum_partials8_kernel<<<2 * K / 8, 256, 0, s>>>(a.partials, a.P, 2 * K, grads_out, desc);
-  else
+  } else {
+    ctx->kernel_name[AMMSB_KN_GRADS_SUM] = "sum_partials_kernel";
     sum_partials_kernel<<<(2 * K + 15) / 16, 256, 0, s>>>(a.partials, a.P, 2 * K, grads_out, desc);
+  }
   AMMSB_LAUNCH_CHECK(ctx);
   return AMMSB_OK;
 }

@@ -29,7 +29,7 @@ extern "C" const char* ammsb_strerror(int code) {
 extern "C" const char* ammsb_last_error(const ammsb_ctx* ctx) { return ctx ? ctx->err : "no context"; }
 
 extern "C" const char* ammsb_last_kernel_name(const ammsb_ctx* ctx, int which) {
-  if (!ctx || which < 0 || which > 4 || !ctx->kernel_name[which]) return "";
+  if (!ctx || which < 0 || which > AMMSB_KN_GRADS_SUM || !ctx->kernel_name[which]) return "";
   return ctx->kernel_name[which];
 }
 
@@ -515,14 +515,18 @@ static int sample_neighbors_common(ammsb_ctx* ctx, ammsb_seed* seeds, const uint
   // them the chip is full either way and 64 nodes per wave use it better (72 vs 132 us)
   if (n == 32 && !per_thread && n_nodes <= 20000) {
     const uint32_t waves = gsize < n_nodes ? gsize : n_nodes;
+    ctx->kernel_name[AMMSB_KN_NBR] = "sample_neighbors_wave_kernel";
     sample_neighbors_wave_kernel<<<div_up(waves, 4), 256, 0, as_stream(stream)>>>(
         seeds, nodes, n_nodes, (uint32_t)ctx->params.N, gsize, table, packed, desc, wg);
-  } else if (lds_bytes <= 64 * 1024)
+  } else if (lds_bytes <= 64 * 1024) {
+    ctx->kernel_name[AMMSB_KN_NBR] = "sample_neighbors_lds_kernel";
     sample_neighbors_lds_kernel<<<div_up(gsize, 64), 64, lds_bytes, as_stream(stream)>>>(
         seeds, nodes, n_nodes, (uint32_t)ctx->params.N, n, gsize, table, packed, desc, wg);
-  else
+  } else {
+    ctx->kernel_name[AMMSB_KN_NBR] = "sample_neighbors_kernel";
     sample_neighbors_kernel<<<div_up(gsize, 64), 64, 0, as_stream(stream)>>>(
         seeds, nodes, n_nodes, (uint32_t)ctx->params.N, n, gsize, table, packed, desc, wg);
+  }
   AMMSB_LAUNCH_CHECK(ctx);
   return AMMSB_OK;
 }

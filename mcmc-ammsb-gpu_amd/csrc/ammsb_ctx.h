@@ -23,13 +23,15 @@ struct ammsb_ctx {
   unsigned long long* ppx_cnt_partials;  // [max_ppx_blocks, 2]
   uint32_t max_ppx_blocks;
   uint32_t* ppx_ticket;      // [1]   blocks of a self-reducing perplexity launch that have written their partials (0 between launches)
-  // name of the kernel the last update_phi / update_pi / beta gradient / perplexity call dispatched to, as the
-  // rocprofv3 kernel trace spells it (ammsb_last_kernel_name)
-  const char* kernel_name[5];
+  // name of the kernel the last update_phi / update_pi / beta gradient / perplexity / neighbour sampler call dispatched
+  // to, and of the partial-row sum that followed the gradient, as the rocprofv3 kernel trace spells it
+  // (ammsb_last_kernel_name)
+  const char* kernel_name[7];
   char err[256];
 };
 
-enum { AMMSB_KN_PHI = 0, AMMSB_KN_PI = 1, AMMSB_KN_GRADS = 2, AMMSB_KN_PPX = 3, AMMSB_KN_PHI_SMALL = 4 };
+enum { AMMSB_KN_PHI = 0, AMMSB_KN_PI = 1, AMMSB_KN_GRADS = 2, AMMSB_KN_PPX = 3, AMMSB_KN_PHI_SMALL = 4, AMMSB_KN_NBR = 5,
+       AMMSB_KN_GRADS_SUM = 6 };
 
 // "kernel<template arguments>" as the demangler prints it; one static string per launcher instantiation
 static inline std::string ammsb_kname(const char* fmt, ...) {

@@ -478,10 +478,10 @@ int launch_ppx_lds(ammsb_ctx* ctx, const PpxArgs& a, hipStream_t s) {
   // two-edge ring: 16 KiB per wave, so the 8 slots per CU the launch asks for are resident at once (a three-edge
   // ring at 24 KiB fits 6 and needs a second round: 0.335 vs 0.250 ms at C3; 1536 slots x 3 edges ties at 0.247)
   const size_t lds = (size_t)2 * 2 * sizeof(float) * 64 * KPT;
-  static const std::string name = ammsb_kname("ppx_lds_kernel<%d, 2u, %d>", KPT, VL);
-  ctx->kernel_name[AMMSB_KN_PPX] = name.c_str();
   // AMMSB_PPX_FOLD=1: the launch reduces its own partials (FOLD instantiation; no ppx_reduce_kernel launch)
   static const bool fold = getenv("AMMSB_PPX_FOLD") && atoi(getenv("AMMSB_PPX_FOLD")) == 1;
+  static const std::string name = ammsb_kname("ppx_lds_kernel<%d, 2u, %d, %s>", KPT, VL, fold ? "true" : "false");
+  ctx->kernel_name[AMMSB_KN_PPX] = name.c_str();
   if (fold) {
     PpxArgs f = a;
     f.ticket = ctx->ppx_ticket;

@@ -126,10 +126,11 @@ class Context:
     def check(self, rc):
         check(rc, self._ctx)
 
-    KERNELS = ("update_phi", "update_pi", "beta_grads", "perplexity", "update_phi_small")
+    KERNELS = ("update_phi", "update_pi", "beta_grads", "perplexity", "update_phi_small", "sample_neighbors",
+               "grads_sum")
 
     def kernel_names(self):
-        """Names of the kernels the last update_phi / update_pi / gradient / perplexity calls on this context
+        """Names of the kernels the last update_phi / update_pi / gradient / perplexity / sampler calls on this context
         dispatched to, spelled as in a rocprofv3 kernel trace (ammsb_last_kernel_name).  "update_phi" is the form large
         launches take, "update_phi_small" the several-waves-per-node form of launches of at most 512 groups (link
         mini-batches); a context that has only ever made small launches reports that one under both keys."""
