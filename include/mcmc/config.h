@@ -76,6 +76,10 @@ struct Config {
 
   // new: draw mini-batches on the device instead of with the host samplers above
   bool device_sampling;
+  // new: with device_sampling, WHICH stream: "own" = the device sampler's xorshift streams and order (the reference's
+  // distribution, another trajectory); "reference" = the reference's rand_r stream and unordered_set orders drawn on the
+  // device from Sample::seed (include/ammsb_refsample.h): host sampling's mini-batches bit for bit.  Not with graph_launch.
+  std::string sampling_stream;
   // new: enqueue-only operators (no Finish() after a launch) and, with device_sampling, a two-stream loop ordered by
   // events instead of host joins.  Results are identical.  The per-kernel times of PrintStats come from event pairs
   // recorded around every launch and read back at the next synchronisation point (loop_timers below).

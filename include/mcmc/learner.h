@@ -39,6 +39,7 @@ class Learner {
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc
+  Float DoSampleReference(Sample* sample);  // ... with sampling_stream "reference": csrc/ammsb_refsample.hip
   bool SerializeDeviceSampler(std::ostream* out);
   void RunAsync(uint32_t max_iters, sig_atomic_t* signaled);  // Config::async_launch + device_sampling
   void RunGraph(uint32_t max_iters, sig_atomic_t* signaled);  // Config::graph_launch: iterations as captured graphs
@@ -92,6 +93,9 @@ class Learner {
   std::unique_ptr<clcuda::Buffer<uint8_t>> mb_workspace_;
   std::unique_ptr<clcuda::Buffer<uint32_t>> mb_count_;
   std::mt19937_64 host_rng_;
+  // Config::sampling_stream == "reference": the reference's rand_r stream on the device (libammsb_refsample.so)
+  bool ref_stream_ = false;
+  void* ref_ = nullptr;  // ammsb_refsample*
   // async loop: per sample, `ready` (sampling done, recorded on the sample's stream) and `consumed` (the
   // iteration that used it is done, recorded on the main stream); weights of the enqueued samples
   void* ev_ready_[2] = {nullptr, nullptr};

@@ -42,6 +42,7 @@ Config::Config() {  // config.h:69-101
   phi_vector_width = 1;
   sum_grads_vector_width = 1;
   device_sampling = false;
+  sampling_stream = "own";
   async_launch = false;
   calc_train_ppx = false;
   training_ppx_ratio = 0.01;  // config.h:72
@@ -131,7 +132,8 @@ std::ostream& operator<<(std::ostream& out, const Config& cfg) {  // config.cc:8
       << "|E|: " << cfg.E << "\n"
       << "phi_mode: " << to_string(cfg.phi_mode) << "\n"
       << "phi_vwidth: " << cfg.phi_vector_width << "\n"
-      << "device_sampling: " << cfg.device_sampling << "\n";
+      << "device_sampling: " << cfg.device_sampling << "\n"
+      << "sampling_stream: " << cfg.sampling_stream << "\n";
   if (cfg.training) out << "|Training edges|: " << cfg.training->Size() << "\n";
   if (cfg.heldout) out << "|Heldout edges|: " << cfg.heldout->Size() << "\n";
   return out;

@@ -5,6 +5,7 @@
 #include "mcmc/learner.h"
 #include "mcmc/exchange.h"
 #include "mcmc/serialize.h"
+#include "ammsb_refsample.h"
 
 #include <hip/hip_runtime.h>
 
@@ -89,6 +90,12 @@ Learner::Learner(const Config& cfg, clcuda::Queue queue)
   }
   samples_[0].reset(new Sample(cfg_, queue_, cfg_.sample_seed[0]));
   samples_[1].reset(new Sample(cfg_, queue_, cfg_.sample_seed[1]));
+  if (cfg_.sampling_stream != "own" && cfg_.sampling_stream != "reference")
+    throw std::runtime_error("sampling_stream must be own or reference (got " + cfg_.sampling_stream + ")");
+  ref_stream_ = cfg_.device_sampling && cfg_.sampling_stream == "reference";
+  if (ref_stream_ && cfg_.graph_launch)
+    throw std::runtime_error("graph_launch does not cover sampling_stream reference: the descriptor loop needs each "
+                             "mini-batch's sizes before the device has drawn it");
   if (cfg_.device_sampling) {
     if (cfg_.strategy != Node && cfg_.strategy != NodeLink && cfg_.strategy != NodeNonLink)
       throw std::runtime_error("device sampling implements Node / NodeLink / NodeNonLink only");
@@ -118,6 +125,19 @@ Learner::Learner(const Config& cfg, clcuda::Queue queue)
     candidates_ = CandidatesForExcluded(max_excluded);
     if (candidates_ == 0)
       throw std::runtime_error("device sampling needs N >= 2 * mini_batch with room for the largest degree");
+    if (ref_stream_) {
+      // the reference's own stream: nothing of the own-stream sampler's state is needed (no candidate streams, no host
+      // generator); each Sample keeps its rand_r seed exactly as with host sampling
+      for (uint64_t u = 0; u < cfg_.N; ++u)
+        for (uint64_t i = off[u]; i < off[u + 1]; ++i)
+          if (tgt[i] == u) throw std::runtime_error("reference-stream sampling: the training graph holds a self-loop");
+      const uint64_t items = std::max<uint64_t>(cfg_.mini_batch_size, cfg_.trainingGraph->MaxFanOut()) + 1;
+      ammsb_refsample* h = nullptr;
+      const int rc = ammsb_refsample_create(queue_.device(), cfg_.N, static_cast<uint32_t>(cfg_.mini_batch_size),
+                                            candidates_, static_cast<uint32_t>(items), &h);
+      if (rc != 0) throw std::runtime_error("ammsb_refsample_create failed: " + std::to_string(rc));
+      ref_ = h;
+    } else {
     mb_rand_.reset(new random::OpenClRandom(queue_, candidates_, cfg_.device_sampling_seed));
     // scrambled states: the reference's {s+i, s'+i} layout makes the streams' first draws collide far too often
     ThrowIfError(ctx_.get(),
@@ -132,6 +152,7 @@ Learner::Learner(const Config& cfg, clcuda::Queue queue)
     const uint32_t zero2[2] = {0, 0};
     mb_count_->Write(queue_, 2, zero2);
     host_rng_.seed(cfg_.device_sampling_host_seed);
+    }
   }
   if (cfg_.async_launch) {
     if (!cfg_.device_sampling) throw std::runtime_error("async_launch needs device_sampling (the host samplers block)");
@@ -240,6 +261,7 @@ void Learner::CheckDeviceSampler() {
       throw std::runtime_error("graph loop: " + std::to_string(timeouts) +
                                " device-side wait(s) timed out (set AMMSB_LOOP_HANDSHAKE=event under kernel-serialising tools)");
   }
+  if (ref_stream_) return;  // a shortfall there throws from DoSampleReference, at the mini-batch that had it
   uint32_t cnt[2] = {0, 0};
   mb_count_->Read(queue_, 2, cnt);
   if (cnt[1] != 0) {
@@ -254,6 +276,10 @@ Learner::~Learner() {
   for (auto& f : futures_)
     if (f.valid()) f.wait();
   if (loop_) ammsb_loop_destroy(loop_);
+  if (ref_) {
+    (void)hipDeviceSynchronize();
+    ammsb_refsample_destroy(static_cast<ammsb_refsample*>(ref_));
+  }
   if (cfg_.async_launch) {
     (void)hipDeviceSynchronize();
     for (int i = 0; i < 2; ++i) {
@@ -326,7 +352,39 @@ Float Learner::EnqueueDevice(Sample* sample, const ammsb_mb_choice& ch) {
                  : static_cast<Float>(2 * cfg_.E) / static_cast<Float>(m);      // sample.cc:292
 }
 
+// Config::sampling_stream == "reference": the mini-batch sampleNode / sampleNodeLink / sampleNodeNonLink +
+// ExtractNodesFromMiniBatch would produce from sample->seed, drawn on the device (include/ammsb_refsample.h).  The host
+// draws the coin and u; the chain runs on the sample's stream and the host waits for that stream only, then reads the
+// 16 result bytes.  One call at a time uses the shared workspace: every call ends with that wait.
+Float Learner::DoSampleReference(Sample* sample) {
+  ammsb_refsample* h = static_cast<ammsb_refsample*>(ref_);
+  hipStream_t stream = static_cast<hipStream_t>(sample->queue.stream());
+  const int strategy = cfg_.strategy == Node ? AMMSB_REFSAMPLE_NODE
+                                             : cfg_.strategy == NodeLink ? AMMSB_REFSAMPLE_NODE_LINK : AMMSB_REFSAMPLE_NODE_NONLINK;
+  uint32_t state = sample->seed, link = 0, u = 0;
+  if (ammsb_refsample_choose(strategy, cfg_.N, degree_.data(), &state, &link, &u) != 0)
+    throw std::runtime_error("reference-stream sampling: no vertex with a training edge");
+  const int rc = link ? ammsb_refsample_link(h, csr_offsets_->data(), csr_targets_->data(), u, degree_[u],
+                                             sample->dev_edges.data(), sample->dev_nodes.data(), stream)
+                      : ammsb_refsample_nonlink(h, u, state, std::min(CandidatesFor(u), candidates_), &trainingSet_->Get(),
+                                                heldoutSet_ ? &heldoutSet_->Get() : nullptr, sample->dev_edges.data(),
+                                                sample->dev_nodes.data(), stream);
+  if (rc != 0) throw std::runtime_error(std::string("reference-stream sampling failed: ") + ammsb_refsample_last_error(h));
+  clcuda::Check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+  const ammsb_refsample_result r = *ammsb_refsample_result_ptr(h);
+  if (r.shortfall)
+    throw std::runtime_error("device mini-batch sampler: a mini-batch found fewer than mini_batch_size distinct non-links (" +
+                             std::to_string(r.n_edges) + ")");
+  sample->seed = ammsb_refsample_jump(state, r.consumed);
+  sample->num_edges = r.n_edges;
+  sample->num_nodes = r.n_nodes;
+  sample->neighbor_sampler(sample->num_nodes, &sample->dev_nodes);
+  const uint32_t m = static_cast<uint32_t>(cfg_.mini_batch_size);
+  return link ? static_cast<Float>(cfg_.N) : static_cast<Float>(2 * cfg_.E) / static_cast<Float>(m);  // sample.cc:268, :292
+}
+
 Float Learner::DoSampleDevice(Sample* sample) {
+  if (ref_stream_) return DoSampleReference(sample);
   const int idx = sample == samples_[0].get() ? 0 : 1;
   choice_[idx] = ChooseDevice();
   return EnqueueDevice(sample, choice_[idx]);
@@ -692,12 +750,15 @@ void Learner::RunAsync(uint32_t max_iters, sig_atomic_t* signaled) {
   if (!enqueued_[phase_]) enqueue_sample(phase_);
   for (uint64_t i = 0; i < max_iters && (signaled ? !*signaled : true); ++i, ++stepCount_) {
     const Float weight = weights_[phase_];
-    enqueue_sample(1 - phase_);
+    // (reference stream: drawing a mini-batch ends with a host wait for its 16 result bytes on the sample's stream;
+    // the step goes to the main stream first, so that the wait overlaps it.  Same launches per stream either way.)
+    if (!ref_stream_) enqueue_sample(1 - phase_);
     Sample& s = *samples_[phase_];
     clcuda::Check(hipStreamWaitEvent(main, static_cast<hipEvent_t>(ev_ready_[phase_]), 0), "hipStreamWaitEvent");
     Step(s, weight);
     clcuda::Check(hipEventRecord(static_cast<hipEvent_t>(ev_consumed_[phase_]), main), "hipEventRecord");
     consumed_valid_[phase_] = true;
+    if (ref_stream_) enqueue_sample(1 - phase_);
     enqueued_[phase_] = false;
     edges_done_ += s.num_edges;
     phase_ = 1 - phase_;
@@ -853,6 +914,14 @@ bool Learner::Serialize(std::ostream* out) {
   }
   props.weight = weight;
   queue_.Finish();
+  if (ref_stream_)  // the Sample records carry the host lists (sample.h:62-75), which live on the device only here:
+    for (auto& smp : samples_) {  // with them the file is what host sampling writes, and either mode resumes from it
+      smp->queue.Finish();
+      smp->edges.resize(smp->num_edges);
+      smp->nodes_vec.resize(smp->num_nodes);
+      if (smp->num_edges) smp->dev_edges.Read(smp->queue, smp->num_edges, smp->edges.data());
+      if (smp->num_nodes) smp->dev_nodes.Read(smp->queue, smp->num_nodes, smp->nodes_vec.data());
+    }
   GatherShardedState();
   return ::mcmc::Serialize(out, &beta_, &queue_) && ::mcmc::Serialize(out, &theta_, &queue_) &&
          ::mcmc::Serialize(out, pi_.get(), &queue_) && ::mcmc::Serialize(out, &phi_, &queue_) &&
@@ -866,7 +935,7 @@ bool Learner::Serialize(std::ostream* out) {
 // Trailing extension (the reference's Parse stops after the two samples): the device sampler's host generator,
 // the sizes of the mini-batches sitting in the sample buffers, and its candidate streams.
 bool Learner::SerializeDeviceSampler(std::ostream* out) {
-  if (!cfg_.device_sampling) return true;
+  if (!cfg_.device_sampling || ref_stream_) return true;  // reference stream: the Sample records say everything
   std::ostringstream st;
   st << host_rng_ << " " << samples_[0]->num_edges << " " << samples_[0]->num_nodes << " " << samples_[1]->num_edges
      << " " << samples_[1]->num_nodes << " " << edges_done_;
@@ -878,7 +947,7 @@ bool Learner::SerializeDeviceSampler(std::ostream* out) {
 }
 
 bool Learner::ParseDeviceSampler(std::istream* in) {
-  if (!cfg_.device_sampling) return true;
+  if (!cfg_.device_sampling || ref_stream_) return true;
   SampleStorage ext;
   if (!ParseMessage(in, &ext) || ext.edges != "AMMSB-DEVSAMPLER-CPP-1") return false;
   std::istringstream st(ext.nodes_vec);

@@ -123,6 +123,14 @@ int main(int argc, char** argv) {
       Opt("sample-seed0", 0, &cfg.sample_seed[0], "1804289383 (new: rand_r seeds of the two sample buffers)"),
       Opt("sample-seed1", 0, &cfg.sample_seed[1], "846930886 (new)"),
       Opt("device-sampling", 0, &cfg.device_sampling, "0 (new: draw mini-batches on the device)"),
+      Option{"sampling-stream", 0,
+             "own (new, with --device-sampling 1: own | reference; reference = the reference's rand_r stream and "
+             "unordered_set orders drawn on the device from --sample-seed0/1, host sampling's mini-batches bit for bit; "
+             "not with --graph 1)",
+             [&cfg](const std::string& v) {
+               cfg.sampling_stream = v;
+               return v == "own" || v == "reference";
+             }},
       Opt("async", 0, &cfg.async_launch, "0 (new: enqueue-only loop; needs --device-sampling 1)"),
       Opt("graph", 0, &cfg.graph_launch, "0 (new: iterations as captured hipGraphs; needs --async 1)"),
       Opt("loop-timers", 0, &cfg.loop_timers, "1 (new: per-kernel device times in PrintStats under --async / --graph)"),
@@ -175,6 +183,11 @@ int main(int argc, char** argv) {
     }
     if (!opt->set(value)) Fatal("the argument ('" + value + "') for option '--" + opt->name + "' is invalid");
   }
+  if (cfg.sampling_stream == "reference" && cfg.graph_launch)
+    Fatal("--sampling-stream reference cannot be combined with --graph 1: the descriptor loop needs each mini-batch's "
+          "sizes before the device has drawn it (use --async 1 without --graph, or the synchronous loop)");
+  if (cfg.sampling_stream == "reference" && !cfg.device_sampling)
+    Fatal("--sampling-stream reference needs --device-sampling 1 (without it the host samplers draw that same stream)");
   if (!loadDataset && !FileExists(filename)) Fatal("Failed to detect file: " + filename);  // main.cc:91-96
   if (loadDataset && loadFile.empty()) Fatal("load-file is required with load-data");
   if (dumpDataset && dumpFile.empty()) Fatal("dump-file is required with dump-data");

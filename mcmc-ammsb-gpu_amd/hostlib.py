@@ -170,8 +170,9 @@ class Dataset:
         nh = self.lib.ammsb_host_dataset_num_heldout(self._h)
         self.training_edges = np.ctypeslib.as_array(self.lib.ammsb_host_dataset_training_edges(self._h),
                                                     shape=(max(nt, 1),))[:nt].copy()
-        self.heldout_edges = np.ctypeslib.as_array(self.lib.ammsb_host_dataset_heldout_edges(self._h),
-                                                   shape=(max(nh, 1),))[:nh].copy()
+        # (a data set without held-out edges has no such array: heldout_ratio 0)
+        self.heldout_edges = (np.ctypeslib.as_array(self.lib.ammsb_host_dataset_heldout_edges(self._h),
+                                                    shape=(nh,)).copy() if nh else np.zeros(0, dtype=np.uint64))
         self.training = HostSet(_handle=self.lib.ammsb_host_dataset_training_set(self._h), _owner=self)
         hs = self.lib.ammsb_host_dataset_heldout_set(self._h)
         self.heldout = HostSet(_handle=hs, _owner=self) if hs else None

@@ -73,6 +73,11 @@ class Config:
         self.sample_seeds = (1804289383, 846930886)  # (new) Sample::seed = rand() twice, sample.cc:132
         self.device_sampling = False                 # (new) draw mini-batches on the device
         self.device_sampling_seed = (1234, 5678)     # (new)
+        self.sampling_stream = "own"                 # (new) with device_sampling: "own" = the device sampler's xorshift
+                                                     # streams and order (same distribution as the reference, another
+                                                     # trajectory); "reference" = the reference's rand_r stream and
+                                                     # unordered_set orders drawn on the device from Sample::seed --
+                                                     # the host sampler's mini-batches bit for bit (eager loop only)
         self.sample_parallel = True                  # MCMC_SAMPLE_PARALLEL, CMakeLists.txt:42
         self.phi_chunks = 4                          # (new) multi-GPU: phi launches per iteration (exchange overlap)
         self.phi_replicate = "auto"                  # (new) multi-GPU: fraction of groups every rank computes itself
@@ -139,6 +144,23 @@ def _check_kernel_variant_knobs(cfg):
                       "are the same" % int(cfg.sum_grads_vector_width))
 
 
+def _check_sampling_stream(cfg):
+    """Config.sampling_stream: True if mini-batches are the reference's rand_r stream drawn on the device.  Refused
+    combinations raise before anything is allocated."""
+    mode = str(getattr(cfg, "sampling_stream", "own"))
+    if mode not in ("own", "reference"):
+        raise AmmsbError("sampling_stream must be own or reference (got %r)" % (mode,))
+    if not (cfg.device_sampling and mode == "reference"):
+        return False
+    if cfg.strategy not in ("Node", "NodeLink", "NodeNonLink"):
+        raise AmmsbError("device sampling implements Node / NodeLink / NodeNonLink only")
+    if cfg.graph_launch is True:
+        raise AmmsbError("graph_launch does not cover sampling_stream='reference': the descriptor loop needs each "
+                         "mini-batch's sizes before the device has drawn it; use graph_launch='auto' or False (the "
+                         "eager loop)")
+    return True
+
+
 class Sample:
     """sample.h:51-92: one of the two mini-batch buffers with its own queue (stream)."""
 
@@ -177,6 +199,7 @@ class Learner:
         self.sharded = self.world > 1 or bool(getattr(cfg, "force_exchange", False))
         cfg.N, cfg.E = dataset.N, dataset.E
         _check_kernel_variant_knobs(cfg)
+        self.ref_stream = _check_sampling_stream(cfg)
         if cfg.alpha == 0:
             cfg.alpha = float(np.float32(1.0) / np.float32(cfg.K))  # main.cc:153
         self.params = ops.make_params(cfg.N, cfg.K, cfg.E, cfg.num_node_sample, cfg.alpha, cfg.a, cfg.b, cfg.c,
@@ -228,20 +251,27 @@ class Learner:
             self.samples.append(Sample(self, cfg.sample_seeds[1]))
         self.phase = 0
         self.futures = [None, None]
-        self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=1) if not cfg.device_sampling else None
+        # the reference stream's worker waits for 16 result bytes per mini-batch: off the main thread, like host sampling
+        self.pool = (concurrent.futures.ThreadPoolExecutor(max_workers=1)
+                     if not cfg.device_sampling or self.ref_stream else None)
         self.dev_sampler = None
+        self.ref_sampler = None
         self.loop = None
         self._loop_dirty = False
         if cfg.device_sampling:
-            off, tgt = dataset.training_csr()
+            off, tgt = dataset.training_csr()  # the host Graph's adjacency order (Graph::ExportCSR)
             # held-out links of a vertex are invalid non-link partners too (sample.cc:283-285)
             he = np.ascontiguousarray(dataset.heldout_edges, dtype=np.uint64)
             he = he[dataset.heldout.Has(he)] if he.size else he
             ends = np.concatenate([he >> np.uint64(32), he & np.uint64(0xFFFFFFFF)]).astype(np.int64)
             hdeg = np.bincount(ends, minlength=N)[:N]
-            self.dev_sampler = ops.DeviceMiniBatchSampler(c, off, tgt, self.trainingSet, self.heldoutSet,
-                                                          cfg.mini_batch_size, cfg.device_sampling_seed,
-                                                          heldout_degree=hdeg)
+            if self.ref_stream:
+                self.ref_sampler = ops.ReferenceStreamSampler(c, off, tgt, self.trainingSet, self.heldoutSet,
+                                                              cfg.mini_batch_size, heldout_degree=hdeg)
+            else:
+                self.dev_sampler = ops.DeviceMiniBatchSampler(c, off, tgt, self.trainingSet, self.heldoutSet,
+                                                              cfg.mini_batch_size, cfg.device_sampling_seed,
+                                                              heldout_degree=hdeg)
         # multi-GPU: how the beta gradient is computed (Config.beta_grads)
         self.grads_mode, self.grads_fused = "sharded", False
         if self.sharded:
@@ -293,6 +323,10 @@ class Learner:
             if self.dev_sampler is not None:
                 sample.choice = self.dev_sampler.choose(cfg.strategy)
                 ne, nv, weight = self.dev_sampler.enqueue(sample.choice, sample.dev_edges, sample.dev_nodes)
+            elif self.ref_sampler is not None:
+                # waits for the result bytes on sample.stream only (in the sampling worker when sample_parallel)
+                ne, nv, weight, sample.seed = self.ref_sampler.enqueue(cfg.strategy, sample.seed, sample.dev_edges,
+                                                                       sample.dev_nodes)
             else:
                 edges, nodes, weight, sample.seed = self.dataset.sample(cfg.mini_batch_size, cfg.strategy,
                                                                         sample.seed)
@@ -900,6 +934,12 @@ class Learner:
         self.ops.synchronize()
         if self.dev_sampler is not None:
             self.dev_sampler.check()
+        if self.ref_sampler is not None:
+            # the Sample records carry the host lists (sample.h:62-75); here they live on the device only.  With them
+            # the file is what host sampling writes, so either mode resumes from it.
+            for s in self.samples:
+                s.edges = self.ops.to_numpy(s.dev_edges[:s.n_edges]).view(np.uint64).copy()
+                s.nodes_vec = self.ops.to_numpy(s.dev_nodes[:s.n_nodes]).view(np.uint32).copy()
         ck.write_buffer(out, self.beta)
         ck.write_buffer(out, self.theta)
         ck.write_rpm(out, self.pi)
@@ -1000,3 +1040,6 @@ class Learner:
         self._loop_dirty = False
         if self.pool is not None:
             self.pool.shutdown(wait=True)
+        if self.ref_sampler is not None:
+            self.ref_sampler.close()  # its device workspace and pinned result page
+            self.ref_sampler = None

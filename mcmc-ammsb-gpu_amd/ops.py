@@ -685,6 +685,131 @@ class DeviceMiniBatchSampler:
         self.queue = [(int(a), int(b)) for a, b in st.get("queue", [])]
 
 
+class ReferenceStreamSampler:
+    """The reference's own mini-batch stream on the device (include/ammsb_refsample.h): from a Sample::seed exactly
+    the edges, the node list (both in the reference's std::unordered_set iteration order), the weight and the seed
+    afterwards that mcmc::sampleNode / sampleNodeLink / sampleNodeNonLink + ExtractNodesFromMiniBatch produce on the
+    host (host/sample.cc), with no host-to-device copy of edges or nodes.  The host draws the coin and u (a few rand_r
+    calls); candidates, de-duplication, both orders run on the device; 16 result bytes come back through host-mapped
+    pinned memory.  Calls are serialised by the read of that result: one sampler serves both Samples."""
+
+    def __init__(self, ctx, csr_offsets, csr_targets, training_set, heldout_set, mini_batch, heldout_degree=None,
+                 capacity=None):
+        from . import _refsample
+        self.ctx = ctx
+        self.rs = _refsample
+        self.lib = _refsample.load()
+        self.N = int(ctx.params.N)
+        self.E = int(ctx.params.E)
+        self.m = int(mini_batch)
+        off = np.ascontiguousarray(csr_offsets, dtype=np.uint64)
+        tgt = np.ascontiguousarray(csr_targets, dtype=np.uint32)
+        self.degree = np.ascontiguousarray(np.diff(off.astype(np.int64)), dtype=np.uint32)
+        if tgt.size and (tgt == np.repeat(np.arange(self.N, dtype=np.uint32), self.degree)).any():
+            raise AmmsbError("reference-stream sampling: the training graph holds a self-loop")
+        self.excluded = self.degree.astype(np.int64) + 1
+        if heldout_degree is not None:
+            self.excluded = self.excluded + np.asarray(heldout_degree, dtype=np.int64)
+        self.max_fan_out = int(self.degree.max()) if self.degree.size else 0
+        self.offsets = ctx.from_numpy(off.view(np.int64))
+        self.targets = ctx.from_numpy(tgt.view(np.int32))
+        self.training_set, self.heldout_set = training_set, heldout_set
+        self._cand = {}
+        # candidate capacity: the existing device sampler's sizing rule (ammsb_minibatch_candidates_for)
+        self.C = int(capacity) if capacity is not None else self._candidates_for(int(self.excluded.max()))
+        if self.C == 0:
+            raise AmmsbError("device sampling needs N >= 2 * mini_batch with room for the largest degree "
+                             "(N=%d, m=%d, max excluded=%d)" % (self.N, self.m, int(self.excluded.max())))
+        # the longest list the ordering kernel may write: Dataset.max_edges(m) edges, one node more -- buffers handed to
+        # enqueue() must hold that many (the Learner's Sample buffers do)
+        self.max_items = max(self.m, self.max_fan_out) + 1
+        self._h = C.c_void_p()
+        rc = self.lib.ammsb_refsample_create(ctx.device.index, self.N, self.m, self.C, self.max_items,
+                                             C.byref(self._h))
+        if rc != 0:
+            raise AmmsbError("ammsb_refsample_create failed: %d (N=%d, m=%d, capacity=%d)" % (rc, self.N, self.m, self.C))
+        self.result = self.lib.ammsb_refsample_result_ptr(self._h)
+        self.num_epochs = int(self.lib.ammsb_refsample_num_epochs(self._h))
+        self.w_link = float(np.float32(self.N))                               # sample.cc:268
+        self.w_nonlink = float(np.float32(2 * self.E) / np.float32(self.m))   # sample.cc:292
+        self.shortfalls = 0   # sticky: mini-batches that found fewer than m distinct non-links among their candidates
+        self.last_consumed = 0
+        self._done = torch.cuda.Event()
+
+    def _candidates_for(self, excluded):
+        key = (int(excluded) + 31) // 32 * 32
+        c = self._cand.get(key)
+        if c is None:
+            c = self._cand[key] = int(self.ctx.lib.ammsb_minibatch_candidates_for(self.N, self.m, key))
+        return c
+
+    def candidates(self, u):
+        """Candidates a non-link mini-batch around u draws (never more than the capacity)."""
+        return min(self._candidates_for(self.excluded[u]), self.C)
+
+    def choose(self, strategy, seed):
+        """The host's share: (link, u, seed once u is known)."""
+        code = self.rs.STRATEGIES.get(strategy)
+        if code is None:
+            raise AmmsbError("device sampling implements Node / NodeLink / NodeNonLink only")
+        s, link, u = C.c_uint32(int(seed)), C.c_uint32(0), C.c_uint32(0)
+        rc = self.lib.ammsb_refsample_choose(code, self.N, self.degree.ctypes.data, C.byref(s), C.byref(link),
+                                             C.byref(u))
+        if rc != 0:
+            raise AmmsbError("reference-stream sampling: no vertex with a training edge (rc %d)" % rc)
+        return bool(link.value), int(u.value), int(s.value)
+
+    def enqueue(self, strategy, seed, dev_edges, dev_nodes):
+        """Draw one mini-batch from `seed` on the current stream and wait for its 16 result bytes (this stream only).
+        Returns (n_edges, n_nodes, weight, seed afterwards)."""
+        link, u, state = self.choose(strategy, seed)
+        if int(dev_edges.numel()) < self.max_items - 1 or int(dev_nodes.numel()) < self.max_items:
+            raise AmmsbError("reference-stream sampling: the buffers hold %d edges / %d nodes, a mini-batch may have %d / %d"
+                             % (dev_edges.numel(), dev_nodes.numel(), self.max_items - 1, self.max_items))
+        if link:
+            rc = self.lib.ammsb_refsample_link(self._h, _ptr(self.offsets), _ptr(self.targets), u, int(self.degree[u]),
+                                               _ptr(dev_edges), _ptr(dev_nodes), _stream())
+        else:
+            hs = C.byref(self.heldout_set.desc) if self.heldout_set is not None else None
+            rc = self.lib.ammsb_refsample_nonlink(self._h, u, state, self.candidates(u),
+                                                  C.byref(self.training_set.desc), hs, _ptr(dev_edges),
+                                                  _ptr(dev_nodes), _stream())
+        if rc != 0:
+            raise AmmsbError("reference-stream sampling failed: %d (%s)"
+                             % (rc, self.lib.ammsb_refsample_last_error(self._h).decode()))
+        self._done.record(_torch_stream())
+        self._done.synchronize()
+        r = self.result.contents
+        ne, nv, consumed, short = int(r.n_edges), int(r.n_nodes), int(r.consumed), int(r.shortfall)
+        self.last_consumed = consumed
+        if short:
+            self.shortfalls += 1
+            raise AmmsbError("device mini-batch sampler: %d mini-batch(es) found fewer than %d distinct non-links "
+                             "(last count %d)" % (self.shortfalls, self.m, ne))
+        return ne, nv, (self.w_link if link else self.w_nonlink), self.rs.jump(state, consumed)
+
+    __call__ = enqueue
+
+    def check(self):
+        """Raise if a mini-batch since the last check came up short (enqueue raises at once; this is for a caller that
+        caught that and went on)."""
+        if self.shortfalls:
+            n, self.shortfalls = self.shortfalls, 0
+            raise AmmsbError("device mini-batch sampler: %d mini-batch(es) found fewer than %d distinct non-links"
+                             % (n, self.m))
+
+    def close(self):
+        if self._h:
+            self.lib.ammsb_refsample_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
