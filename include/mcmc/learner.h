@@ -36,6 +36,21 @@ class Learner {
   std::vector<Float> GetPiRow(Vertex v);
   uint64_t MiniBatchEdges() const { return edges_done_; }
 
+  // Reading the model out (include/ammsb_readout.h; not in the reference API).  Per node its `top` (1..16) strongest
+  // communities, value descending and equal values by community ascending: ids / weights are [N, top], a slot below
+  // `threshold` (>= 0) or past K holds 0xFFFFFFFF / 0; count[a] = communities >= threshold, not capped at top;
+  // sizes[k] = nodes with pi[a, k] >= threshold.  Any of the four may be nullptr.  Waits for the work in flight as
+  // Serialize does, reads this rank's pi (every rank holds all of it: not a collective) in row slabs of bounded
+  // output, and touches nothing of the iteration.  Throws std::invalid_argument on a bad top / threshold.
+  void Memberships(uint32_t top, Float threshold, std::vector<uint32_t>* ids, std::vector<Float>* weights,
+                   std::vector<uint32_t>* count, std::vector<uint64_t>* sizes);
+  // ... and as communities: members of community k = members[offsets[k] .. offsets[k + 1]), ascending node ids; a
+  // node is a member of the communities in its non-empty Memberships slots.  sizes as above (may be nullptr).
+  void Communities(uint32_t top, Float threshold, std::vector<uint64_t>* offsets, std::vector<uint32_t>* members,
+                   std::vector<uint64_t>* sizes);
+  // `# N K top threshold`, then one line `k size n0 n1 ...` per community.
+  bool WriteCommunities(std::ostream* out, uint32_t top, Float threshold);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

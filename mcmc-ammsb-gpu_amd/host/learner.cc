@@ -6,12 +6,14 @@
 #include "mcmc/exchange.h"
 #include "mcmc/serialize.h"
 #include "ammsb_refsample.h"
+#include "ammsb_readout.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <iostream>
@@ -1023,6 +1025,76 @@ std::vector<Float> Learner::GetTheta() {
   theta_.Read(queue_, v.size(), v.data());
   return v;
 }
+// ---- reading the model out: libammsb_readout.so over pi, in row slabs whose outputs stay under a fixed byte budget
+void Learner::Memberships(uint32_t top, Float threshold, std::vector<uint32_t>* ids, std::vector<Float>* weights,
+                          std::vector<uint32_t>* count, std::vector<uint64_t>* sizes) {
+  if (top == 0 || top > AMMSB_READOUT_MAX_TOP) throw std::invalid_argument("Memberships: top must be in 1..16");
+  if (!(threshold >= 0)) throw std::invalid_argument("Memberships: the threshold must be >= 0");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  const bool tops = ids || weights || count;
+  const uint64_t slab = std::min<uint64_t>(std::max<uint64_t>(N, 1), (64ull << 20) / (8ull * top + 4));
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint32_t> d_ids(context, tops ? slab * top : 1), d_count(context, tops ? slab : 1);
+  clcuda::Buffer<Float> d_weights(context, tops ? slab * top : 1);
+  std::unique_ptr<clcuda::Buffer<uint64_t>> d_sizes;
+  if (sizes) {
+    sizes->assign(K, 0);
+    d_sizes.reset(new clcuda::Buffer<uint64_t>(context, queue_, sizes->begin(), sizes->end()));
+  }
+  if (ids) ids->resize(N * top);
+  if (weights) weights->resize(N * top);
+  if (count) count->resize(N);
+  for (uint64_t lo = 0; lo < N; lo += slab) {
+    const uint64_t n = std::min(slab, N - lo);
+    const int rc = ammsb_readout_top(&pi_->Get(), nullptr, lo, n, top, threshold, tops ? d_ids() : nullptr,
+                                     tops ? d_weights() : nullptr, tops ? d_count() : nullptr,
+                                     d_sizes ? (*d_sizes)() : nullptr, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw std::runtime_error(std::string("ammsb_readout_top: ") + ammsb_strerror(rc) + " (" + ammsb_readout_last_error() + ")");
+    if (ids) d_ids.Read(queue_, n * top, ids->data() + lo * top);
+    if (weights) d_weights.Read(queue_, n * top, weights->data() + lo * top);
+    if (count) d_count.Read(queue_, n, count->data() + lo);
+  }
+  if (sizes) d_sizes->Read(queue_, K, sizes->data());
+  queue_.Finish();
+}
+
+void Learner::Communities(uint32_t top, Float threshold, std::vector<uint64_t>* offsets, std::vector<uint32_t>* members,
+                          std::vector<uint64_t>* sizes) {
+  std::vector<uint32_t> ids;
+  Memberships(top, threshold, &ids, nullptr, nullptr, sizes);
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  offsets->assign(K + 1, 0);
+  for (uint32_t id : ids)
+    if (id != AMMSB_READOUT_NONE) ++(*offsets)[id + 1];
+  for (uint64_t k = 0; k < K; ++k) (*offsets)[k + 1] += (*offsets)[k];
+  members->assign((*offsets)[K], 0);
+  std::vector<uint64_t> fill(offsets->begin(), offsets->end() - 1);
+  for (uint64_t a = 0; a < N; ++a)  // ascending nodes, so every community's list comes out ascending
+    for (uint32_t t = 0; t < top; ++t) {
+      const uint32_t id = ids[a * top + t];
+      if (id != AMMSB_READOUT_NONE) (*members)[fill[id]++] = static_cast<uint32_t>(a);
+    }
+}
+
+bool Learner::WriteCommunities(std::ostream* out, uint32_t top, Float threshold) {
+  std::vector<uint64_t> offsets, sizes;
+  std::vector<uint32_t> members;
+  Communities(top, threshold, &offsets, &members, &sizes);
+  const uint64_t K = pi_->Cols();
+  char thr[32];
+  snprintf(thr, sizeof(thr), "%.9g", static_cast<double>(threshold));
+  *out << "# " << pi_->Rows() << " " << K << " " << top << " " << thr << "\n";
+  for (uint64_t k = 0; k < K; ++k) {
+    *out << k << " " << sizes[k];
+    for (uint64_t i = offsets[k]; i < offsets[k + 1]; ++i) *out << " " << members[i];
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
 std::vector<Float> Learner::GetPiRow(Vertex v) {
   std::vector<Float> row(cfg_.K);
   const uint32_t blk = v / pi_->RowsPerBlock();

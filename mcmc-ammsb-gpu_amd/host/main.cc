@@ -76,7 +76,10 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut;
+  bool haveMembershipTop = false, haveMembershipThreshold = false;
+  long membershipTop = 4;
+  double membershipThreshold = 0;
   int deviceId = -1;
   mcmc::Config cfg;
   uint32_t max_iters = 100;
@@ -143,6 +146,21 @@ int main(int argc, char** argv) {
       Opt("device", 0, &deviceId, "-1 (new: HIP device; default LOCAL_RANK with --exchange, else 0)"),
       OptStr("checkpoint-in", 0, &ckptIn),    // (new) Learner::Parse before the first iteration
       OptStr("checkpoint-out", 0, &ckptOut),  // (new) Learner::Serialize after the last one
+      OptStr("communities-out", 0, &communitiesOut),  // (new) after the last perplexity line: `# N K top threshold`, then `k size n0 n1 ...` per community
+      Option{"membership-top", 0, "4 (new, with --communities-out: strongest communities kept per node, 1..16)",
+             [&](const std::string& v) {
+               haveMembershipTop = true;
+               std::istringstream in(v);
+               in >> membershipTop;
+               return !in.fail() && in.eof();
+             }},
+      Option{"membership-threshold", 0, "0 (new, with --communities-out: a node is a member where pi >= this)",
+             [&](const std::string& v) {
+               haveMembershipThreshold = true;
+               std::istringstream in(v);
+               in >> membershipThreshold;
+               return !in.fail() && in.eof();
+             }},
   };
   for (int i = 1; i < argc; ++i) {
     std::string arg = argv[i], value;
@@ -188,6 +206,10 @@ int main(int argc, char** argv) {
           "sizes before the device has drawn it (use --async 1 without --graph, or the synchronous loop)");
   if (cfg.sampling_stream == "reference" && !cfg.device_sampling)
     Fatal("--sampling-stream reference needs --device-sampling 1 (without it the host samplers draw that same stream)");
+  if ((haveMembershipTop || haveMembershipThreshold) && communitiesOut.empty())
+    Fatal("--membership-top / --membership-threshold need --communities-out FILE");
+  if (membershipTop < 1 || membershipTop > 16) Fatal("--membership-top must be in 1..16");
+  if (!(membershipThreshold >= 0)) Fatal("--membership-threshold must be >= 0");
   if (!loadDataset && !FileExists(filename)) Fatal("Failed to detect file: " + filename);  // main.cc:91-96
   if (loadDataset && loadFile.empty()) Fatal("load-file is required with load-data");
   if (dumpDataset && dumpFile.empty()) Fatal("dump-file is required with dump-data");
@@ -262,6 +284,19 @@ int main(int argc, char** argv) {
     // Serialize is a collective with an exchange; the states are identical afterwards and rank 0's file is the checkpoint
     std::ofstream out(rank == 0 ? ckptOut : std::string("/dev/null"), std::ios::binary);
     if (!learner.Serialize(&out)) Fatal("cannot write checkpoint " + ckptOut);
+  }
+  if (!communitiesOut.empty()) {
+    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(communitiesOut);
+        if (!out.good() || !learner.WriteCommunities(&out, static_cast<uint32_t>(membershipTop),
+                                                     static_cast<mcmc::Float>(membershipThreshold)))
+          Fatal("cannot write communities " + communitiesOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("communities: ") + e.what());
+    }
   }
   learner.PrintStats();
   return 0;

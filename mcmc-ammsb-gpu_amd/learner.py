@@ -1027,6 +1027,58 @@ class Learner:
         if self.dev_sampler is not None:
             self.dev_sampler.check()  # a mini-batch that came up short is an error, never a silent duplicate
 
+    # ---- reading the model out (include/ammsb_readout.h).  Every rank holds all of pi, so these are local on any rank
+    # and are not collectives.  Nothing of the iteration is touched: no RNG stream, no counter, no buffer.
+    READOUT_SLAB_BYTES = 64 << 20  # most output bytes (ids + weights + count) one library call writes
+
+    def _readout(self):
+        if getattr(self, "_community_readout", None) is None:
+            self._community_readout = self.ops.CommunityReadout(self.ctx)
+        return self._community_readout
+
+    def Memberships(self, top=4, threshold=0.0, nodes=None, sizes=None):
+        """-> (ids [n, top] int32, weights [n, top] float32, count [n] int32), device tensors: per node (all of them, or
+        the list `nodes`) its `top` strongest communities, value descending and equal values by community ascending;
+        a slot below `threshold` (or past K) holds id -1 (0xFFFFFFFF) and weight 0; count = communities >= threshold,
+        not capped at `top`.  sizes: a zeroed [K] int64 device tensor that receives the community sizes of the same
+        pass."""
+        from . import _readout
+        top, threshold = _readout.check_args(top, threshold)
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the read-out has no CPU path")
+        self.drain()
+        ro, c = self._readout(), self.ctx
+        if nodes is not None and not torch.is_tensor(nodes):
+            nodes = c.from_numpy(np.ascontiguousarray(nodes, dtype=np.uint32))
+        n = self.cfg.N if nodes is None else int(nodes.numel())
+        slab = max(1, self.READOUT_SLAB_BYTES // (8 * top + 4))
+        if n <= slab:
+            return ro.top(self.pi, top, threshold, nodes=nodes, sizes=sizes)
+        ids, weights = c.empty((n, top), torch.int32), c.empty((n, top), torch.float32)
+        count = c.empty((n,), torch.int32)
+        for lo in range(0, n, slab):
+            hi = min(lo + slab, n)
+            i, w, k = ro.top(self.pi, top, threshold, nodes=None if nodes is None else nodes[lo:hi],
+                             rows=(lo, hi) if nodes is None else None, sizes=sizes)
+            ids[lo:hi], weights[lo:hi], count[lo:hi] = i, w, k
+        return ids, weights, count
+
+    def CommunitySizes(self, threshold):
+        """-> [K] int64 device tensor: nodes with pi[a, k] >= threshold."""
+        from . import _readout
+        _, threshold = _readout.check_args(1, threshold)
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the read-out has no CPU path")
+        self.drain()
+        return self._readout().sizes(self.pi, threshold)
+
+    def Communities(self, top=4, threshold=0.0):
+        """-> host CSR (offsets [K+1] int64, members int32): the members of each community in ascending node order.  A
+        node is a member of the communities in its non-empty Memberships slots, so `top` caps memberships per node."""
+        from . import _readout
+        ids, _, _ = self.Memberships(top, threshold)
+        return _readout.communities_csr(ids.cpu().numpy(), self.cfg.K)
+
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
         out("SAMPLING : %.6f (%%%.2f)" % (self.samplingTime, 100 * self.samplingTime / max(self.time, 1e-12)))

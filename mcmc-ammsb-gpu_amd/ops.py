@@ -810,6 +810,57 @@ class ReferenceStreamSampler:
             pass
 
 
+class CommunityReadout:
+    """The read-out of a fitted pi (include/ammsb_readout.h): per row the T strongest communities with their weights
+    (value descending, equal values by column ascending), the number of columns >= thr, and per community the number of
+    rows >= thr.  Exact: weights are the stored values.  Owns nothing but the output tensors it returns; ids come back
+    as int32 (torch has no arithmetic on uint32), so the empty slot 0xFFFFFFFF reads -1."""
+
+    def __init__(self, ctx):
+        from . import _readout
+        self.ctx = ctx
+        self.ro = _readout
+        self.lib = _readout.load()
+
+    def top(self, pi, T, thr, nodes=None, rows=None, sizes=None):
+        """-> (ids [n, T] int32, weights [n, T] float32, count [n] int32) on the device, for rows `rows` = (lo, hi) of
+        pi (default: all) or for the device / host list `nodes`.  sizes: a [K] int64 device tensor to accumulate the
+        community sizes of these rows into (the caller zeroes it)."""
+        T, thr = self.ro.check_args(T, thr)
+        if nodes is not None:
+            if rows is not None:
+                raise AmmsbError("read-out: give nodes or rows, not both")
+            if not torch.is_tensor(nodes):
+                nodes = self.ctx.from_numpy(np.ascontiguousarray(nodes, dtype=np.uint32))
+            if nodes.dtype != torch.int32 or not nodes.is_contiguous():
+                raise AmmsbError("read-out: nodes must be a contiguous int32 (uint32 bits) device tensor")
+            lo, n = 0, int(nodes.numel())
+        else:
+            lo, hi = (0, pi.rows) if rows is None else (int(rows[0]), int(rows[1]))
+            if not 0 <= lo <= hi <= pi.rows:
+                raise AmmsbError("read-out: rows (%d, %d) outside 0..%d" % (lo, hi, pi.rows))
+            n = hi - lo
+        if sizes is not None and (sizes.dtype != torch.int64 or sizes.numel() != pi.cols or not sizes.is_contiguous()):
+            raise AmmsbError("read-out: sizes must be a contiguous [K] int64 device tensor")
+        ids = self.ctx.empty((n, T), torch.int32)
+        weights = self.ctx.empty((n, T), torch.float32)
+        count = self.ctx.empty((n,), torch.int32)
+        self.ro.check(self.lib.ammsb_readout_top(C.byref(pi.desc), _ptr(nodes), lo, n, T, thr, _ptr(ids),
+                                                 _ptr(weights), _ptr(count), _ptr(sizes), _stream()))
+        return ids, weights, count
+
+    def sizes(self, pi, thr, out=None):
+        """-> [K] int64: rows of pi with pi[a, k] >= thr (one pass, nothing else written)."""
+        _, thr = self.ro.check_args(1, thr)
+        out = self.ctx.zeros((pi.cols,), torch.int64) if out is None else out
+        self.ro.check(self.lib.ammsb_readout_top(C.byref(pi.desc), None, 0, pi.rows, 1, thr, None, None, None,
+                                                 _ptr(out), _stream()))
+        return out
+
+    def kernel_name(self):
+        return self.ro.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
