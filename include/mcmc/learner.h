@@ -51,6 +51,21 @@ class Learner {
   // `# N K top threshold`, then one line `k size n0 n1 ...` per community.
   bool WriteCommunities(std::ostream* out, uint32_t top, Float threshold);
 
+  // Predicting links (include/ammsb_linkpred.h; not in the reference API).  p(a, b) = eps + sum_k pi_ak pi_bk
+  // (beta_k - eps) per edge key of `edges` (either order of the ends; -1 for an end >= N) ...
+  void LinkProbabilities(const std::vector<Edge>& edges, std::vector<Float>* out);
+  // ... and per node of `nodes` its `top` (1..64) most probable partners among all N nodes that are not the node itself
+  // and whose pair is in none of the edge sets named by exclude_mask: ids / scores are [nodes.size(), top], score
+  // descending and equal scores by id ascending, 0xFFFFFFFF / 0 in the slots past the eligible nodes.  Both wait for the
+  // work in flight as Serialize does, read this rank's pi (not a collective), go in query slabs of bounded output, and
+  // touch nothing of the iteration.  Throw std::invalid_argument on a bad top, mask or node id >= N.
+  enum : uint32_t { kExcludeTraining = 1u, kExcludeHeldout = 2u };
+  void PredictLinks(const std::vector<Vertex>& nodes, uint32_t top, uint32_t exclude_mask, std::vector<Vertex>* ids,
+                    std::vector<Float>* scores);
+  // `# N K top exclude` (exclude: none | training | heldout | all), then one line `a n b0 s0 b1 s1 ...` per query node
+  // (n = its non-empty slots); scores printed with %.9g, so they parse back to the same binary32.
+  bool WritePredictedLinks(std::ostream* out, const std::vector<Vertex>& nodes, uint32_t top, uint32_t exclude_mask);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

@@ -7,6 +7,7 @@
 #include "mcmc/serialize.h"
 #include "ammsb_refsample.h"
 #include "ammsb_readout.h"
+#include "ammsb_linkpred.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1090,6 +1091,80 @@ bool Learner::WriteCommunities(std::ostream* out, uint32_t top, Float threshold)
   for (uint64_t k = 0; k < K; ++k) {
     *out << k << " " << sizes[k];
     for (uint64_t i = offsets[k]; i < offsets[k + 1]; ++i) *out << " " << members[i];
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- predicting links: libammsb_linkpred.so over (pi, beta), eps as the kernels hold it (MakeKernelParams)
+void Learner::LinkProbabilities(const std::vector<Edge>& edges, std::vector<Float>* out) {
+  DrainAsync();
+  queue_.Finish();
+  out->assign(edges.size(), 0);
+  if (edges.empty()) return;
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Edge> d_edges(context, queue_, edges.begin(), edges.end());
+  clcuda::Buffer<Float> d_out(context, edges.size());
+  const int rc = ammsb_linkpred_pairs(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), edges.size(),
+                                      d_out(), queue_.stream());
+  if (rc != AMMSB_OK)
+    throw std::runtime_error(std::string("ammsb_linkpred_pairs: ") + ammsb_strerror(rc) + " (" + ammsb_linkpred_last_error() + ")");
+  d_out.Read(queue_, edges.size(), out->data());
+  queue_.Finish();
+}
+
+void Learner::PredictLinks(const std::vector<Vertex>& nodes, uint32_t top, uint32_t exclude_mask,
+                           std::vector<Vertex>* ids, std::vector<Float>* scores) {
+  if (top == 0 || top > AMMSB_LINKPRED_MAX_TOP) throw std::invalid_argument("PredictLinks: top must be in 1..64");
+  if (exclude_mask & ~(kExcludeTraining | kExcludeHeldout)) throw std::invalid_argument("PredictLinks: unknown exclude bits");
+  const uint64_t N = pi_->Rows(), K = pi_->Cols(), Q = nodes.size();
+  for (Vertex v : nodes)
+    if (v >= N) throw std::invalid_argument("PredictLinks: a node id >= N");
+  DrainAsync();
+  queue_.Finish();
+  ids->assign(Q * top, AMMSB_LINKPRED_NONE);
+  scores->assign(Q * top, 0);
+  if (Q == 0) return;
+  const ammsb_set* ex[2] = {nullptr, nullptr};
+  int n_ex = 0;
+  if (exclude_mask & kExcludeTraining) ex[n_ex++] = &trainingSet_->Get();
+  if ((exclude_mask & kExcludeHeldout) && heldoutSet_) ex[n_ex++] = &heldoutSet_->Get();
+  // whole tiles of 128 queries whose outputs stay under a fixed byte budget; the workspace does not grow with Q
+  const uint64_t slab = std::min<uint64_t>(Q, std::max<uint64_t>(128, (64ull << 20) / (8ull * top) / 128 * 128));
+  const uint64_t ws_bytes = ammsb_linkpred_top_workspace_bytes(static_cast<uint32_t>(slab), top, N, K);
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Vertex> d_nodes(context, queue_, nodes.begin(), nodes.end()), d_ids(context, slab * top);
+  clcuda::Buffer<Float> d_scores(context, slab * top);
+  clcuda::Buffer<uint64_t> d_ws(context, (ws_bytes + 7) / 8);
+  const Float eps = MakeKernelParams(cfg_).epsilon;
+  for (uint64_t lo = 0; lo < Q; lo += slab) {
+    const uint64_t n = std::min(slab, Q - lo);
+    const int rc = ammsb_linkpred_top(&pi_->Get(), beta_.data(), eps, d_nodes() + lo, static_cast<uint32_t>(n), top, ex[0],
+                                      ex[1], 0, N, d_ids(), d_scores(), d_ws(), ws_bytes, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw std::runtime_error(std::string("ammsb_linkpred_top: ") + ammsb_strerror(rc) + " (" + ammsb_linkpred_last_error() + ")");
+    d_ids.Read(queue_, n * top, ids->data() + lo * top);
+    d_scores.Read(queue_, n * top, scores->data() + lo * top);
+  }
+  queue_.Finish();
+}
+
+bool Learner::WritePredictedLinks(std::ostream* out, const std::vector<Vertex>& nodes, uint32_t top,
+                                  uint32_t exclude_mask) {
+  std::vector<Vertex> ids;
+  std::vector<Float> scores;
+  PredictLinks(nodes, top, exclude_mask, &ids, &scores);
+  static const char* const kNames[4] = {"none", "training", "heldout", "all"};
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << top << " " << kNames[exclude_mask & 3u] << "\n";
+  char num[32];
+  for (size_t i = 0; i < nodes.size(); ++i) {
+    uint32_t n = 0;
+    while (n < top && ids[i * top + n] != AMMSB_LINKPRED_NONE) ++n;
+    *out << nodes[i] << " " << n;
+    for (uint32_t t = 0; t < n; ++t) {
+      snprintf(num, sizeof(num), "%.9g", static_cast<double>(scores[i * top + t]));
+      *out << " " << ids[i * top + t] << " " << num;
+    }
     *out << "\n";
   }
   return static_cast<bool>(*out);

@@ -76,7 +76,9 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude;
+  bool haveLinksTop = false;
+  long linksTop = 10;
   bool haveMembershipTop = false, haveMembershipThreshold = false;
   long membershipTop = 4;
   double membershipThreshold = 0;
@@ -147,6 +149,16 @@ int main(int argc, char** argv) {
       OptStr("checkpoint-in", 0, &ckptIn),    // (new) Learner::Parse before the first iteration
       OptStr("checkpoint-out", 0, &ckptOut),  // (new) Learner::Serialize after the last one
       OptStr("communities-out", 0, &communitiesOut),  // (new) after the last perplexity line: `# N K top threshold`, then `k size n0 n1 ...` per community
+      OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
+      Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
+             [&](const std::string& v) {
+               haveLinksTop = true;
+               std::istringstream in(v);
+               in >> linksTop;
+               return !in.fail() && in.eof();
+             }},
+      OptStr("links-nodes", 0, &linksNodes),      // (new, with --links-out) file of query node ids; default: every node
+      OptStr("links-exclude", 0, &linksExclude),  // (new, with --links-out) none | training | all (default: training and held-out edges)
       Option{"membership-top", 0, "4 (new, with --communities-out: strongest communities kept per node, 1..16)",
              [&](const std::string& v) {
                haveMembershipTop = true;
@@ -210,6 +222,24 @@ int main(int argc, char** argv) {
     Fatal("--membership-top / --membership-threshold need --communities-out FILE");
   if (membershipTop < 1 || membershipTop > 16) Fatal("--membership-top must be in 1..16");
   if (!(membershipThreshold >= 0)) Fatal("--membership-threshold must be >= 0");
+  if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
+    Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
+  if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
+  uint32_t linksMask = mcmc::Learner::kExcludeTraining | mcmc::Learner::kExcludeHeldout;
+  if (linksExclude == "none") linksMask = 0;
+  else if (linksExclude == "training") linksMask = mcmc::Learner::kExcludeTraining;
+  else if (!linksExclude.empty() && linksExclude != "all") Fatal("--links-exclude must be none, training or all");
+  std::vector<mcmc::Vertex> linkNodes;
+  if (!linksNodes.empty()) {
+    std::ifstream in(linksNodes);
+    if (!in.good()) Fatal("cannot read --links-nodes file " + linksNodes);
+    unsigned long long v;
+    while (in >> v) {
+      if (v > 0xFFFFFFFFull) Fatal("--links-nodes: node id " + std::to_string(v) + " is not a node id");
+      linkNodes.push_back(static_cast<mcmc::Vertex>(v));
+    }
+    if (!in.eof()) Fatal("--links-nodes: " + linksNodes + " holds something that is not a node id");
+  }
   if (!loadDataset && !FileExists(filename)) Fatal("Failed to detect file: " + filename);  // main.cc:91-96
   if (loadDataset && loadFile.empty()) Fatal("load-file is required with load-data");
   if (dumpDataset && dumpFile.empty()) Fatal("dump-file is required with dump-data");
@@ -227,6 +257,8 @@ int main(int argc, char** argv) {
   if (!mcmc::GenerateSetsFromEdges(cfg.N, unique_edges, cfg.heldout_ratio, &cfg.training_edges, &cfg.heldout_edges,
                                    &cfg.training, &cfg.heldout))
     Fatal("Failed to generate training/heldout sets");
+  for (mcmc::Vertex v : linkNodes)
+    if (v >= cfg.N) Fatal("--links-nodes: node id " + std::to_string(v) + " >= N = " + std::to_string(cfg.N));
   cfg.trainingGraph.reset(new mcmc::Graph(cfg.N, cfg.training_edges));
   cfg.heldoutGraph.reset(new mcmc::Graph(cfg.N, cfg.heldout_edges));
   if (cfg.alpha == 0) cfg.alpha = static_cast<mcmc::Float>(1) / cfg.K;  // main.cc:153
@@ -296,6 +328,22 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("communities: ") + e.what());
+    }
+  }
+  if (!linksOut.empty()) {
+    // every rank holds all of pi: link prediction is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        if (linksNodes.empty()) {
+          linkNodes.resize(cfg.N);
+          for (uint64_t v = 0; v < cfg.N; ++v) linkNodes[v] = static_cast<mcmc::Vertex>(v);
+        }
+        std::ofstream out(linksOut);
+        if (!out.good() || !learner.WritePredictedLinks(&out, linkNodes, static_cast<uint32_t>(linksTop), linksMask))
+          Fatal("cannot write links " + linksOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("links: ") + e.what());
     }
   }
   learner.PrintStats();

@@ -1079,6 +1079,62 @@ class Learner:
         ids, _, _ = self.Memberships(top, threshold)
         return _readout.communities_csr(ids.cpu().numpy(), self.cfg.K)
 
+    # ---- predicting links (include/ammsb_linkpred.h).  Like the read-out: drained first, local on any rank, no CPU
+    # path, and nothing of the iteration is touched.
+    LINKPRED_SLAB_BYTES = 64 << 20  # most output bytes (ids + scores) one library call writes
+
+    def _linkpred(self):
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: link prediction has no CPU path")
+        if getattr(self, "_link_predictor", None) is None:
+            self._link_predictor = self.ops.LinkPredictor(self.ctx)
+        return self._link_predictor
+
+    def LinkProbabilities(self, edges):
+        """-> [n] float32 device tensor: p(a, b) = eps + sum_k pi_ak pi_bk (beta_k - eps) per edge key (host array or
+        device tensor of (a << 32) | b, either order of the ends); -1 for a pair with an end >= N."""
+        lp = self._linkpred()
+        self.drain()
+        return lp.pairs(self.pi, self.beta, self.params.epsilon, edges)
+
+    def PredictLinks(self, nodes, top=10, exclude=("training", "heldout")):
+        """-> (ids [Q, top] int32, scores [Q, top] float32), device tensors: per node of `nodes` the `top` most probable
+        partners among all N nodes that are not the node itself and whose pair is not in the excluded edge sets
+        (`exclude`: any subset of "training", "heldout"); score descending, equal scores by id ascending; a slot past
+        the eligible nodes holds id -1 and score 0."""
+        from . import _linkpred
+        top = _linkpred.check_top(top)
+        names = _linkpred.check_exclude(exclude)
+        lp = self._linkpred()
+        self.drain()
+        c = self.ctx
+        sets = [{"training": self.trainingSet, "heldout": self.heldoutSet}[n] for n in names]
+        if not torch.is_tensor(nodes):
+            nodes = c.from_numpy(np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1))
+        Q = int(nodes.numel())
+        # The workspace does not grow with Q: the library aims at a fixed grid, so a call holds about 2048 x 128 partial
+        # lists whatever Q is (2 MiB x top).  What grows is the output, and that is what a slab bounds (whole tiles of
+        # 128 queries).
+        slab = max(128, self.LINKPRED_SLAB_BYTES // (8 * top) // 128 * 128)
+        if Q <= slab:
+            return lp.top(self.pi, self.beta, self.params.epsilon, nodes, top, exclude=sets)
+        ids, scores = c.empty((Q, top), torch.int32), c.empty((Q, top), torch.float32)
+        for lo in range(0, Q, slab):
+            hi = min(lo + slab, Q)
+            ids[lo:hi], scores[lo:hi] = lp.top(self.pi, self.beta, self.params.epsilon, nodes[lo:hi].contiguous(),
+                                               top, exclude=sets)
+        return ids, scores
+
+    def HeldoutAUC(self):
+        """Area under the ROC curve of LinkProbabilities over the held-out list; label = membership in the held-out
+        set, as the perplexity pass decides is_edge.  Rank statistic with average ranks for ties, float64 on the host
+        (_linkpred.auc); raises when the list lacks links or non-links."""
+        from . import _linkpred
+        self._linkpred()
+        scores = self.LinkProbabilities(self.heldoutEdges)
+        labels = self.heldoutSet.Has(self.heldoutEdges)
+        return _linkpred.auc(scores.cpu().numpy(), labels.cpu().numpy() != 0)
+
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
         out("SAMPLING : %.6f (%%%.2f)" % (self.samplingTime, 100 * self.samplingTime / max(self.time, 1e-12)))

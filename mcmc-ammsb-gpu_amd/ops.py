@@ -861,6 +861,85 @@ class CommunityReadout:
         return self.ro.last_kernel_name()
 
 
+class LinkPredictor:
+    """Link probabilities from a fitted (pi, beta) (include/ammsb_linkpred.h): p(a, b) = eps + sum_k pi_ak pi_bk
+    (beta_k - eps) as a dense block, as the T best candidates per query, or per pair of a list.  Owns the workspace of
+    `top` (the partial lists of the blocks), which only ever grows: reserve() it outside a timed path.  Ids come back as
+    int32, so the empty slot 0xFFFFFFFF reads -1."""
+
+    def __init__(self, ctx):
+        from . import _linkpred
+        self.ctx = ctx
+        self.lp = _linkpred
+        self.lib = _linkpred.load()
+        self.workspace = None
+
+    def _nodes(self, nodes):
+        if not torch.is_tensor(nodes):
+            nodes = self.ctx.from_numpy(np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1))
+        if nodes.dtype != torch.int32 or nodes.dim() != 1 or not nodes.is_contiguous():
+            raise AmmsbError("link prediction: nodes must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        return nodes
+
+    def _range(self, pi, cand):
+        lo, hi = (0, pi.rows) if cand is None else (int(cand[0]), int(cand[1]))
+        if not 0 <= lo <= hi <= pi.rows:
+            raise AmmsbError("link prediction: candidates (%d, %d) outside 0..%d" % (lo, hi, pi.rows))
+        return lo, hi - lo
+
+    def workspace_bytes(self, Q, T, cand_n, K):
+        return int(self.lib.ammsb_linkpred_top_workspace_bytes(int(Q), int(T), int(cand_n), int(K)))
+
+    def reserve(self, nbytes):
+        """Grow the workspace to nbytes (torch's allocator: not for a timed path)."""
+        if self.workspace is None or self.workspace.numel() < nbytes:
+            self.workspace = self.ctx.empty((int(nbytes),), torch.uint8)
+        return self.workspace
+
+    def block(self, pi, beta, epsilon, nodes, cand=None):
+        """-> [Q, n] float32: p(nodes[i], lo + j) for the candidate rows cand = (lo, hi) of pi (default: all)."""
+        nodes = self._nodes(nodes)
+        lo, n = self._range(pi, cand)
+        out = self.ctx.empty((int(nodes.numel()), n), torch.float32)
+        self.lp.check(self.lib.ammsb_linkpred_block(C.byref(pi.desc), _ptr(beta), float(epsilon), _ptr(nodes),
+                                                    int(nodes.numel()), lo, n, _ptr(out), _stream()))
+        return out
+
+    def top(self, pi, beta, epsilon, nodes, T, exclude=(), cand=None):
+        """-> (ids [Q, T] int32, scores [Q, T] float32): per query its T most probable candidates that are not the
+        query itself and whose pair is in none of the DeviceSets `exclude` (at most two); score descending, equal
+        scores by id ascending; -1 / 0 in the slots past the eligible candidates."""
+        T = self.lp.check_top(T)
+        nodes = self._nodes(nodes)
+        lo, n = self._range(pi, cand)
+        exclude = [s for s in exclude if s is not None]
+        if len(exclude) > 2:
+            raise AmmsbError("link prediction: at most two exclusion sets")
+        ex = [C.byref(s.desc) for s in exclude] + [None, None]
+        Q = int(nodes.numel())
+        nbytes = self.workspace_bytes(Q, T, n, pi.cols)
+        ws = self.reserve(nbytes)
+        ids, scores = self.ctx.empty((Q, T), torch.int32), self.ctx.empty((Q, T), torch.float32)
+        self.lp.check(self.lib.ammsb_linkpred_top(C.byref(pi.desc), _ptr(beta), float(epsilon), _ptr(nodes), Q, T,
+                                                  ex[0], ex[1], lo, n, _ptr(ids), _ptr(scores), _ptr(ws), nbytes,
+                                                  _stream()))
+        return ids, scores
+
+    def pairs(self, pi, beta, epsilon, edges):
+        """-> [n] float32: p(a, b) per edge key (a << 32 | b, either order of the ends); -1 for an end >= N."""
+        if not torch.is_tensor(edges):
+            edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
+        if edges.dtype != torch.int64 or edges.dim() != 1 or not edges.is_contiguous():
+            raise AmmsbError("link prediction: edges must be a contiguous 1-d int64 (uint64 bits) device tensor")
+        out = self.ctx.empty((int(edges.numel()),), torch.float32)
+        self.lp.check(self.lib.ammsb_linkpred_pairs(C.byref(pi.desc), _ptr(beta), float(epsilon), _ptr(edges),
+                                                    int(edges.numel()), _ptr(out), _stream()))
+        return out
+
+    def kernel_name(self):
+        return self.lp.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
