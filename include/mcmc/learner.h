@@ -66,6 +66,22 @@ class Learner {
   // (n = its non-empty slots); scores printed with %.9g, so they parse back to the same binary32.
   bool WritePredictedLinks(std::ostream* out, const std::vector<Vertex>& nodes, uint32_t top, uint32_t exclude_mask);
 
+  // The communities that explain a link (include/ammsb_linkcomm.h; not in the reference API).  Per edge key of `edges`
+  // (either order of the ends) the `top` (1..16) largest terms t_k = (pi_ak pi_bk) beta_k that are > 0 and >= min_term,
+  // with their communities: ids / terms are [edges.size(), top], term descending and equal terms by community
+  // ascending, 0xFFFFFFFF / 0 in the empty slots; prob is p(a, b) as LinkProbabilities defines it (-1 and empty slots
+  // for an end >= N).  Terms are exact binary32 products; t_k / p is the posterior that the link is a community-k link.
+  // Waits for the work in flight as Serialize does, reads this rank's pi (not a collective), goes in slabs of bounded
+  // output, and touches nothing of the iteration.  Throws std::invalid_argument on a bad top or min_term.
+  void LinkCommunities(const std::vector<Edge>& edges, uint32_t top, Float min_term, std::vector<uint32_t>* ids,
+                       std::vector<Float>* terms, std::vector<Float>* prob);
+  // sizes: [K + 1], per community the training links whose largest term it holds; sizes[K] = the training links no
+  // community explains at min_term.  One pass that writes nothing else.
+  void LinkCommunitySizes(Float min_term, std::vector<uint64_t>* sizes);
+  // `# N K E top min_term`, then one line `a b p n k0 t0 k1 t1 ...` per training link in ascending key order (n = its
+  // filled slots); floats printed with %.9g, so they parse back to the same binary32.
+  bool WriteLinkCommunities(std::ostream* out, uint32_t top, Float min_term);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

@@ -8,6 +8,7 @@
 #include "ammsb_refsample.h"
 #include "ammsb_readout.h"
 #include "ammsb_linkpred.h"
+#include "ammsb_linkcomm.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1163,6 +1164,93 @@ bool Learner::WritePredictedLinks(std::ostream* out, const std::vector<Vertex>& 
     *out << nodes[i] << " " << n;
     for (uint32_t t = 0; t < n; ++t) {
       snprintf(num, sizeof(num), "%.9g", static_cast<double>(scores[i * top + t]));
+      *out << " " << ids[i * top + t] << " " << num;
+    }
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- the communities that explain a link: libammsb_linkcomm.so over (pi, beta), eps as the kernels hold it
+namespace {
+void CheckLinkCommArgs(const char* who, uint32_t top, Float min_term) {
+  if (top == 0 || top > AMMSB_LINKCOMM_MAX_TOP) throw std::invalid_argument(std::string(who) + ": top must be in 1..16");
+  if (!(min_term >= 0 && std::isfinite(min_term)))
+    throw std::invalid_argument(std::string(who) + ": min_term must be finite and >= 0");
+}
+
+// every training link once, ascending ((min << 32) | max is how an Edge is stored)
+std::vector<Edge> SortedTrainingLinks(const Config& cfg) {
+  std::vector<Edge> links(cfg.training_edges.begin(), cfg.training_edges.end());
+  std::sort(links.begin(), links.end());
+  links.erase(std::unique(links.begin(), links.end()), links.end());
+  return links;
+}
+}  // namespace
+
+void Learner::LinkCommunities(const std::vector<Edge>& edges, uint32_t top, Float min_term, std::vector<uint32_t>* ids,
+                              std::vector<Float>* terms, std::vector<Float>* prob) {
+  CheckLinkCommArgs("LinkCommunities", top, min_term);
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t n_all = edges.size();
+  ids->assign(n_all * top, AMMSB_LINKCOMM_NONE);
+  terms->assign(n_all * top, 0);
+  prob->assign(n_all, 0);
+  if (n_all == 0) return;
+  const uint64_t slab = std::min<uint64_t>(n_all, std::max<uint64_t>(1, (64ull << 20) / (8ull * top + 4)));
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Edge> d_edges(context, queue_, edges.begin(), edges.end());
+  clcuda::Buffer<uint32_t> d_ids(context, slab * top);
+  clcuda::Buffer<Float> d_terms(context, slab * top), d_prob(context, slab);
+  const Float eps = MakeKernelParams(cfg_).epsilon;
+  for (uint64_t lo = 0; lo < n_all; lo += slab) {
+    const uint64_t n = std::min(slab, n_all - lo);
+    const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), eps, d_edges() + lo, n, top, min_term, d_ids(),
+                                        d_terms(), d_prob(), nullptr, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw std::runtime_error(std::string("ammsb_linkcomm_edges: ") + ammsb_strerror(rc) + " (" + ammsb_linkcomm_last_error() + ")");
+    d_ids.Read(queue_, n * top, ids->data() + lo * top);
+    d_terms.Read(queue_, n * top, terms->data() + lo * top);
+    d_prob.Read(queue_, n, prob->data() + lo);
+  }
+  queue_.Finish();
+}
+
+void Learner::LinkCommunitySizes(Float min_term, std::vector<uint64_t>* sizes) {
+  CheckLinkCommArgs("LinkCommunitySizes", 1, min_term);
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t K = pi_->Cols();
+  sizes->assign(K + 1, 0);
+  const std::vector<Edge> links = SortedTrainingLinks(cfg_);
+  if (links.empty()) return;
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Edge> d_edges(context, queue_, links.begin(), links.end());
+  clcuda::Buffer<uint64_t> d_sizes(context, queue_, sizes->begin(), sizes->end());
+  const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), links.size(), 1,
+                                      min_term, nullptr, nullptr, nullptr, d_sizes(), queue_.stream());
+  if (rc != AMMSB_OK)
+    throw std::runtime_error(std::string("ammsb_linkcomm_edges: ") + ammsb_strerror(rc) + " (" + ammsb_linkcomm_last_error() + ")");
+  d_sizes.Read(queue_, K + 1, sizes->data());
+  queue_.Finish();
+}
+
+bool Learner::WriteLinkCommunities(std::ostream* out, uint32_t top, Float min_term) {
+  const std::vector<Edge> links = SortedTrainingLinks(cfg_);
+  std::vector<uint32_t> ids;
+  std::vector<Float> terms, prob;
+  LinkCommunities(links, top, min_term, &ids, &terms, &prob);
+  char num[32];
+  snprintf(num, sizeof(num), "%.9g", static_cast<double>(min_term));
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << links.size() << " " << top << " " << num << "\n";
+  for (size_t i = 0; i < links.size(); ++i) {
+    uint32_t n = 0;
+    while (n < top && ids[i * top + n] != AMMSB_LINKCOMM_NONE) ++n;
+    snprintf(num, sizeof(num), "%.9g", static_cast<double>(prob[i]));
+    *out << (links[i] >> 32) << " " << (links[i] & 0xFFFFFFFFull) << " " << num << " " << n;
+    for (uint32_t t = 0; t < n; ++t) {
+      snprintf(num, sizeof(num), "%.9g", static_cast<double>(terms[i * top + t]));
       *out << " " << ids[i * top + t] << " " << num;
     }
     *out << "\n";

@@ -6,6 +6,7 @@
 #include <signal.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <fstream>
 #include <functional>
@@ -76,7 +77,10 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut;
+  bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
+  long linkCommTop = 1;
+  double linkCommMinTerm = 0;
   bool haveLinksTop = false;
   long linksTop = 10;
   bool haveMembershipTop = false, haveMembershipThreshold = false;
@@ -149,6 +153,21 @@ int main(int argc, char** argv) {
       OptStr("checkpoint-in", 0, &ckptIn),    // (new) Learner::Parse before the first iteration
       OptStr("checkpoint-out", 0, &ckptOut),  // (new) Learner::Serialize after the last one
       OptStr("communities-out", 0, &communitiesOut),  // (new) after the last perplexity line: `# N K top threshold`, then `k size n0 n1 ...` per community
+      OptStr("link-communities-out", 0, &linkCommOut),  // (new) after the last perplexity line: `# N K E top min_term`, then `a b p n k0 t0 k1 t1 ...` per training link
+      Option{"link-communities-top", 0, "1 (new, with --link-communities-out: largest terms kept per link, 1..16)",
+             [&](const std::string& v) {
+               haveLinkCommTop = true;
+               std::istringstream in(v);
+               in >> linkCommTop;
+               return !in.fail() && in.eof();
+             }},
+      Option{"link-communities-min-term", 0, "0 (new, with --link-communities-out: terms below it take no slot)",
+             [&](const std::string& v) {
+               haveLinkCommMinTerm = true;
+               std::istringstream in(v);
+               in >> linkCommMinTerm;
+               return !in.fail() && in.eof();
+             }},
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -222,6 +241,11 @@ int main(int argc, char** argv) {
     Fatal("--membership-top / --membership-threshold need --communities-out FILE");
   if (membershipTop < 1 || membershipTop > 16) Fatal("--membership-top must be in 1..16");
   if (!(membershipThreshold >= 0)) Fatal("--membership-threshold must be >= 0");
+  if ((haveLinkCommTop || haveLinkCommMinTerm) && linkCommOut.empty())
+    Fatal("--link-communities-top / --link-communities-min-term need --link-communities-out FILE");
+  if (linkCommTop < 1 || linkCommTop > 16) Fatal("--link-communities-top must be in 1..16");
+  if (!(linkCommMinTerm >= 0) || !std::isfinite(static_cast<float>(linkCommMinTerm)))
+    Fatal("--link-communities-min-term must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -344,6 +368,19 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("links: ") + e.what());
+    }
+  }
+  if (!linkCommOut.empty()) {
+    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(linkCommOut);
+        if (!out.good() || !learner.WriteLinkCommunities(&out, static_cast<uint32_t>(linkCommTop),
+                                                         static_cast<mcmc::Float>(linkCommMinTerm)))
+          Fatal("cannot write link communities " + linkCommOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("link communities: ") + e.what());
     }
   }
   learner.PrintStats();

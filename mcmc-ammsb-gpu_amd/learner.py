@@ -1135,6 +1135,72 @@ class Learner:
         labels = self.heldoutSet.Has(self.heldoutEdges)
         return _linkpred.auc(scores.cpu().numpy(), labels.cpu().numpy() != 0)
 
+    # ---- the communities that explain a link (include/ammsb_linkcomm.h).  Like the other read-outs: drained first,
+    # local on any rank, no CPU path, and nothing of the iteration is touched.
+    LINKCOMM_SLAB_BYTES = 64 << 20  # most output bytes (ids + terms + prob) one library call writes
+
+    def _linkcomm(self):
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the link-community read-out has no CPU path")
+        if getattr(self, "_link_communities", None) is None:
+            self._link_communities = self.ops.LinkCommunities(self.ctx)
+        return self._link_communities
+
+    def TrainingLinks(self):
+        """-> [E] uint64 (as int64) device tensor: every training link once as (min << 32) | max, ascending.  Built
+        from the data set's training adjacency on first use and kept."""
+        lc = self._linkcomm()
+        if getattr(self, "_training_links", None) is None:
+            off, tgt = self.dataset.training_csr()
+            src = np.repeat(np.arange(self.cfg.N, dtype=np.uint64), np.diff(off.astype(np.int64)))
+            tgt = tgt[:src.size].astype(np.uint64)
+            keep = src < tgt                      # each link sits in both ends' rows: take it from the lower end
+            keys = np.sort((src[keep] << np.uint64(32)) | tgt[keep])
+            self._training_links = lc.ctx.from_numpy(keys)
+        return self._training_links
+
+    def _linkcomm_edges(self, edges):
+        if edges is None:
+            return self.TrainingLinks()
+        if not torch.is_tensor(edges):
+            edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
+        return edges
+
+    def LinkCommunities(self, edges=None, top=1, min_term=0.0):
+        """-> (ids [n, top] int32, share [n, top] float32, prob [n] float32), device tensors: per edge key of `edges`
+        (host array or device tensor of (a << 32) | b, either order of the ends; default: TrainingLinks()) the `top`
+        communities with the largest terms t_k = (pi_ak pi_bk) beta_k that are > 0 and >= min_term, term descending and
+        equal terms by community ascending, and the link's probability p.  share = t_k / p, the posterior that the link
+        is a community-k link: ONE torch division of the kernel's exact terms by its p (so it carries p's rounding),
+        and +0 in an empty slot, whose id is -1 (0xFFFFFFFF); a filled slot has p >= its term > 0.  An edge with an end
+        >= N has empty slots and p = -1.  An empty list gives empty tensors."""
+        from . import _linkcomm
+        top, min_term = _linkcomm.check_args(top, min_term)
+        lc = self._linkcomm()
+        self.drain()
+        edges = self._linkcomm_edges(edges)
+        c, n, eps = self.ctx, int(edges.numel()), self.params.epsilon
+        slab = max(1, self.LINKCOMM_SLAB_BYTES // (8 * top + 4))
+        if n <= slab:
+            ids, terms, prob = lc.edges(self.pi, self.beta, eps, edges, top, min_term)
+        else:
+            ids, terms = c.empty((n, top), torch.int32), c.empty((n, top), torch.float32)
+            prob = c.empty((n,), torch.float32)
+            for lo in range(0, n, slab):
+                hi = min(lo + slab, n)
+                ids[lo:hi], terms[lo:hi], prob[lo:hi] = lc.edges(self.pi, self.beta, eps, edges[lo:hi], top, min_term)
+        share = torch.where(ids < 0, torch.zeros((), dtype=torch.float32, device=terms.device), terms / prob.unsqueeze(1))
+        return ids, share, prob
+
+    def LinkCommunitySizes(self, min_term=0.0, edges=None):
+        """-> [K + 1] int64 device tensor: per community the links (default: the training links) whose largest term it
+        holds; entry K counts the links no community explains at min_term."""
+        from . import _linkcomm
+        _, min_term = _linkcomm.check_args(1, min_term)
+        lc = self._linkcomm()
+        self.drain()
+        return lc.sizes(self.pi, self.beta, self.params.epsilon, self._linkcomm_edges(edges), min_term)
+
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
         out("SAMPLING : %.6f (%%%.2f)" % (self.samplingTime, 100 * self.samplingTime / max(self.time, 1e-12)))

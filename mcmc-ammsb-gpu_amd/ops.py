@@ -940,6 +940,63 @@ class LinkPredictor:
         return self.lp.last_kernel_name()
 
 
+class LinkCommunities:
+    """The communities that explain a link (include/ammsb_linkcomm.h): per edge key the T largest terms
+    (pi[a,k] * pi[b,k]) * beta_k with their communities (term descending, equal terms by community ascending), the
+    link's probability, and per community the number of edges whose largest term it holds.  Exact: ids and terms are
+    the stable argsort of the float32 statement.  Owns nothing but the tensors it returns; ids come back as int32, so
+    the empty slot 0xFFFFFFFF reads -1."""
+
+    def __init__(self, ctx):
+        from . import _linkcomm
+        self.ctx = ctx
+        self.lc = _linkcomm
+        self.lib = _linkcomm.load()
+
+    def _edges(self, edges):
+        if not torch.is_tensor(edges):
+            edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
+        if edges.dtype != torch.int64 or edges.dim() != 1 or not edges.is_contiguous():
+            raise AmmsbError("link communities: edges must be a contiguous 1-d int64 (uint64 bits) device tensor")
+        return edges
+
+    def _sizes(self, pi, sizes):
+        if sizes is not None and (sizes.dtype != torch.int64 or sizes.numel() != pi.cols + 1
+                                  or not sizes.is_contiguous()):
+            raise AmmsbError("link communities: sizes must be a contiguous [K + 1] int64 device tensor")
+        return sizes
+
+    def edges(self, pi, beta, epsilon, edges, top, min_term=0.0, sizes=None):
+        """-> (ids [n, top] int32, terms [n, top] float32, prob [n] float32) on the device.  sizes: a [K + 1] int64
+        device tensor to accumulate into (the caller zeroes it): sizes[k] counts the edges whose slot 0 holds k,
+        sizes[K] the edges with valid ends and no term >= min_term."""
+        top, min_term = self.lc.check_args(top, min_term)
+        edges = self._edges(edges)
+        sizes = self._sizes(pi, sizes)
+        n = int(edges.numel())
+        ids, terms = self.ctx.empty((n, top), torch.int32), self.ctx.empty((n, top), torch.float32)
+        prob = self.ctx.empty((n,), torch.float32)
+        if n == 0:  # a valid no-op; the empty tensors have no address, which the library would read as "no output"
+            return ids, terms, prob
+        self.lc.check(self.lib.ammsb_linkcomm_edges(C.byref(pi.desc), _ptr(beta), float(epsilon), _ptr(edges), n, top,
+                                                    min_term, _ptr(ids), _ptr(terms), _ptr(prob), _ptr(sizes),
+                                                    _stream()))
+        return ids, terms, prob
+
+    def sizes(self, pi, beta, epsilon, edges, min_term=0.0, out=None):
+        """-> [K + 1] int64: the sizes-only pass (nothing else is written)."""
+        _, min_term = self.lc.check_args(1, min_term)
+        edges = self._edges(edges)
+        out = self.ctx.zeros((pi.cols + 1,), torch.int64) if out is None else self._sizes(pi, out)
+        self.lc.check(self.lib.ammsb_linkcomm_edges(C.byref(pi.desc), _ptr(beta), float(epsilon), _ptr(edges),
+                                                    int(edges.numel()), 1, min_term, None, None, None, _ptr(out),
+                                                    _stream()))
+        return out
+
+    def kernel_name(self):
+        return self.lc.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
