@@ -82,6 +82,18 @@ class Learner {
   // filled slots); floats printed with %.9g, so they parse back to the same binary32.
   bool WriteLinkCommunities(std::ostream* out, uint32_t top, Float min_term);
 
+  // Scoring communities against the graph (include/ammsb_quality.h; not in the reference API).  Node a is a member of
+  // community k iff pi[a, k] >= threshold (a binary32 compare).  Over the training links: size [K] = the members of k (as
+  // Memberships' sizes), internal [K] = the links with both ends in k, boundary [K] = the links with exactly one end in
+  // k, uncovered = the links whose ends share no community.  Exact counts.  Waits for the work in flight as Serialize
+  // does, reads this rank's pi (not a collective), and touches nothing of the iteration.  Throws std::invalid_argument
+  // on a threshold that is negative, NaN or infinite.
+  void CommunityQuality(Float threshold, std::vector<uint64_t>* size, std::vector<uint64_t>* internal,
+                        std::vector<uint64_t>* boundary, uint64_t* uncovered);
+  // `# N K E threshold uncovered`, then one line `k size internal boundary conductance density` per community, the
+  // derived measures as include/ammsb_quality.h defines them (-1 where undefined); floats printed with %.9g.
+  bool WriteCommunityQuality(std::ostream* out, Float threshold);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

@@ -9,6 +9,7 @@
 #include "ammsb_readout.h"
 #include "ammsb_linkpred.h"
 #include "ammsb_linkcomm.h"
+#include "ammsb_quality.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1254,6 +1255,59 @@ bool Learner::WriteLinkCommunities(std::ostream* out, uint32_t top, Float min_te
       *out << " " << ids[i * top + t] << " " << num;
     }
     *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- scoring communities against the graph: libammsb_quality.so over pi and the training links
+void Learner::CommunityQuality(Float threshold, std::vector<uint64_t>* size, std::vector<uint64_t>* internal,
+                               std::vector<uint64_t>* boundary, uint64_t* uncovered) {
+  if (!(threshold >= 0 && std::isfinite(threshold)))
+    throw std::invalid_argument("CommunityQuality: the threshold must be finite and >= 0");
+  Memberships(1, threshold, nullptr, nullptr, nullptr, size);  // (drains; sizes only)
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  internal->assign(K, 0);
+  boundary->assign(K, 0);
+  *uncovered = 0;
+  const std::vector<Edge> links = SortedTrainingLinks(cfg_);
+  if (links.empty() || N == 0) return;
+  const uint64_t words = ammsb_quality_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
+  if (words == 0) throw std::runtime_error("CommunityQuality: K outside 1..8192");
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint64_t> d_mask(context, words);
+  clcuda::Buffer<Edge> d_edges(context, queue_, links.begin(), links.end());
+  std::vector<uint64_t> counts(2 * K + 2, 0);
+  clcuda::Buffer<uint64_t> d_counts(context, queue_, counts.begin(), counts.end());
+  int rc = ammsb_quality_mask(&pi_->Get(), threshold, d_mask(), queue_.stream());
+  if (rc == AMMSB_OK)
+    rc = ammsb_quality_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), links.size(), d_counts(), nullptr,
+                             queue_.stream());
+  if (rc != AMMSB_OK)
+    throw std::runtime_error(std::string("ammsb_quality: ") + ammsb_strerror(rc) + " (" + ammsb_quality_last_error() + ")");
+  d_counts.Read(queue_, 2 * K + 2, counts.data());
+  queue_.Finish();
+  std::copy(counts.begin(), counts.begin() + K, internal->begin());
+  std::copy(counts.begin() + K, counts.begin() + 2 * K, boundary->begin());
+  *uncovered = counts[2 * K];
+}
+
+bool Learner::WriteCommunityQuality(std::ostream* out, Float threshold) {
+  std::vector<uint64_t> size, internal, boundary;
+  uint64_t uncovered = 0;
+  CommunityQuality(threshold, &size, &internal, &boundary, &uncovered);
+  const uint64_t links = SortedTrainingLinks(cfg_).size();  // (a training link has both ends < N: none is skipped)
+  char num[32], num2[32];
+  snprintf(num, sizeof(num), "%.9g", static_cast<double>(threshold));
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << links << " " << num << " " << uncovered << "\n";
+  for (size_t k = 0; k < size.size(); ++k) {
+    // float64, as include/ammsb_quality.h states the measures
+    const uint64_t vol = 2 * internal[k] + boundary[k], low = std::min(vol, 2 * links - vol);
+    const double cond = low ? static_cast<double>(boundary[k]) / static_cast<double>(low) : -1.0;
+    const double sz = static_cast<double>(size[k]);
+    const double dens = size[k] >= 2 ? static_cast<double>(internal[k]) / (sz * (sz - 1.0) / 2.0) : -1.0;
+    snprintf(num, sizeof(num), "%.9g", cond);
+    snprintf(num2, sizeof(num2), "%.9g", dens);
+    *out << k << " " << size[k] << " " << internal[k] << " " << boundary[k] << " " << num << " " << num2 << "\n";
   }
   return static_cast<bool>(*out);
 }

@@ -77,7 +77,9 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut;
+  bool haveQualityThreshold = false;
+  double qualityThreshold = 0.05;
   bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
   long linkCommTop = 1;
   double linkCommMinTerm = 0;
@@ -168,6 +170,14 @@ int main(int argc, char** argv) {
                in >> linkCommMinTerm;
                return !in.fail() && in.eof();
              }},
+      OptStr("community-quality-out", 0, &qualityOut),  // (new) after the last perplexity line: `# N K E threshold uncovered`, then `k size internal boundary conductance density` per community
+      Option{"community-quality-threshold", 0, "0.05 (new, with --community-quality-out: a node is a member of k iff pi[a, k] >= it)",
+             [&](const std::string& v) {
+               haveQualityThreshold = true;
+               std::istringstream in(v);
+               in >> qualityThreshold;
+               return !in.fail() && in.eof();
+             }},
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -246,6 +256,9 @@ int main(int argc, char** argv) {
   if (linkCommTop < 1 || linkCommTop > 16) Fatal("--link-communities-top must be in 1..16");
   if (!(linkCommMinTerm >= 0) || !std::isfinite(static_cast<float>(linkCommMinTerm)))
     Fatal("--link-communities-min-term must be finite and >= 0");
+  if (haveQualityThreshold && qualityOut.empty()) Fatal("--community-quality-threshold needs --community-quality-out FILE");
+  if (!(qualityThreshold >= 0) || !std::isfinite(static_cast<float>(qualityThreshold)))
+    Fatal("--community-quality-threshold must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -381,6 +394,18 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("link communities: ") + e.what());
+    }
+  }
+  if (!qualityOut.empty()) {
+    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(qualityOut);
+        if (!out.good() || !learner.WriteCommunityQuality(&out, static_cast<mcmc::Float>(qualityThreshold)))
+          Fatal("cannot write community quality " + qualityOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("community quality: ") + e.what());
     }
   }
   learner.PrintStats();

@@ -1201,6 +1201,45 @@ class Learner:
         self.drain()
         return lc.sizes(self.pi, self.beta, self.params.epsilon, self._linkcomm_edges(edges), min_term)
 
+    # ---- scoring communities against the graph (include/ammsb_quality.h).  Like the other read-outs: drained first,
+    # local on any rank, no CPU path, and nothing of the iteration is touched.
+    def _quality(self):
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the community-quality read-out has no CPU path")
+        if getattr(self, "_community_quality", None) is None:
+            self._community_quality = self.ops.CommunityQuality(self.ctx)
+        return self._community_quality
+
+    def CommunityQuality(self, threshold=0.05, edges=None):
+        """-> _quality.Quality: per community its size (CommunitySizes(threshold)), the links of `edges` (host array or
+        device tensor of (a << 32) | b, either order of the ends; default: TrainingLinks()) with both ends in it
+        (internal) and with exactly one end in it (boundary), membership being pi[a, k] >= threshold; the links no
+        community covers (uncovered), the keys with an end >= N (skipped), links = the others; and, in float64 on the
+        host, conductance and density per community and the coverage of the cover (-1 where undefined).  Counts are
+        exact."""
+        from . import _quality
+        threshold = _quality.check_threshold(threshold)
+        cq = self._quality()
+        self.drain()
+        edges = self._linkcomm_edges(edges)
+        N, K = self.cfg.N, self.cfg.K
+        counts = cq.edges(cq.mask(self.pi, threshold), N, K, edges).cpu().numpy()
+        size = self._readout().sizes(self.pi, threshold).cpu().numpy()
+        skipped = int(counts[2 * K + 1])
+        return _quality.Quality(threshold, size, counts[:K], counts[K:2 * K], int(edges.numel()) - skipped,
+                                int(counts[2 * K]), skipped)
+
+    def SharedCommunities(self, edges=None, threshold=0.05):
+        """-> [n] int32 device tensor: per edge key the number of communities that hold both its ends (pi >= threshold
+        at both), -1 for a key with an end >= N.  An empty list gives an empty tensor."""
+        from . import _quality
+        threshold = _quality.check_threshold(threshold)
+        cq = self._quality()
+        self.drain()
+        edges = self._linkcomm_edges(edges)
+        _, shared = cq.edges(cq.mask(self.pi, threshold), self.cfg.N, self.cfg.K, edges, shared=True, counts=False)
+        return shared
+
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
         out("SAMPLING : %.6f (%%%.2f)" % (self.samplingTime, 100 * self.samplingTime / max(self.time, 1e-12)))

@@ -997,6 +997,53 @@ class LinkCommunities:
         return self.lc.last_kernel_name()
 
 
+class CommunityQuality:
+    """Scoring communities against a graph (include/ammsb_quality.h): one membership bit per (node, community) from one
+    streaming pass over pi, then per edge of a list two rows of bits: per community the edges inside it and the edges
+    that leave it, the edges no community covers, and per edge the communities its ends share.  Integer counts over
+    binary32 compares: exact.  Owns nothing but the tensors it returns."""
+
+    def __init__(self, ctx):
+        from . import _quality
+        self.ctx = ctx
+        self.q = _quality
+        self.lib = _quality.load()
+
+    def mask(self, pi, thr):
+        """-> the membership bits of (pi, thr): an opaque int64 device tensor for edges() (its layout is the library's)"""
+        thr = self.q.check_threshold(thr)
+        words = int(self.lib.ammsb_quality_mask_bytes(pi.desc.num_rows, pi.cols)) // 8
+        if words == 0:
+            raise AmmsbError("community quality: no mask for a %d x %d pi" % (pi.desc.num_rows, pi.cols))
+        out = self.ctx.empty((words,), torch.int64)
+        self.q.check(self.lib.ammsb_quality_mask(C.byref(pi.desc), thr, _ptr(out), _stream()))
+        return out
+
+    def edges(self, mask, N, K, edges, shared=False, counts=True):
+        """mask: what mask() returned for an N x K pi; edges: keys (a << 32) | b, a host array or a contiguous 1-d int64
+        (uint64 bits) device tensor.  -> counts [2K + 2] int64 on the device (internal[0..K), boundary[K..2K),
+        uncovered, skipped), or (counts, shared [n] int32) with shared=True; counts=False leaves the counters out
+        (-> None in their place)."""
+        if not torch.is_tensor(edges):
+            edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
+        if edges.dtype != torch.int64 or edges.dim() != 1 or not edges.is_contiguous():
+            raise AmmsbError("community quality: edges must be a contiguous 1-d int64 (uint64 bits) device tensor")
+        N, K, n = int(N), int(K), int(edges.numel())
+        if mask.dtype != torch.int64 or not mask.is_contiguous() or \
+                not mask.numel() or mask.numel() * 8 != int(self.lib.ammsb_quality_mask_bytes(N, K)):
+            raise AmmsbError("community quality: not the mask of a %d x %d pi" % (N, K))
+        if not counts and not shared:
+            raise AmmsbError("community quality: no output asked for")
+        cnt = self.ctx.zeros((2 * K + 2,), torch.int64) if counts else None
+        sh = self.ctx.empty((n,), torch.int32) if shared else None
+        if n:  # (an empty list is a valid no-op; its empty tensors have no address)
+            self.q.check(self.lib.ammsb_quality_edges(_ptr(mask), N, K, _ptr(edges), n, _ptr(cnt), _ptr(sh), _stream()))
+        return (cnt, sh) if shared else cnt
+
+    def kernel_name(self):
+        return self.q.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
