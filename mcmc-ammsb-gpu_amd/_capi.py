@@ -122,24 +122,36 @@ _OTHER_RES = {"ammsb_strerror": C.c_char_p, "ammsb_last_error": C.c_char_p, "amm
 _lib = None
 
 
+def bind_library(path, signatures, what=""):
+    """dlopen `path` and bind name -> (restype, argtypes) for every entry of `signatures`.  A missing library is an
+    error (`what` is added to its message): there is no other implementation of what a library does."""
+    if not os.path.exists(path):
+        raise AmmsbError("%s not found: build it with `make -C mcmc-ammsb-gpu_amd/csrc` "
+                         "(or __graft_entry__.build())%s" % (path, what))
+    # One HIP runtime per process: torch carries its own libamdhip64, and device pointers / streams are
+    # handed from torch to this library.  Loading torch first makes the library bind to that copy; the
+    # other order gives two runtimes that cannot see each other's devices.
+    import torch  # noqa: F401
+    lib = C.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
+        fn.restype, fn.argtypes = res, args
+    return lib
+
+
+def raise_for(rc, prefix, detail):
+    """AmmsbError for a non-zero return code of one of the post-fit libraries; detail() is its last_error text"""
+    if rc != 0:
+        raise AmmsbError("%s call failed: %d (%s)" % (prefix, rc, detail().decode()))
+
+
 def load(path=None):
     """dlopen the HIP library and bind every symbol include/ammsb.h declares."""
     global _lib
     if _lib is not None and path is None:
         return _lib
-    so = path or LIB_PATH
-    if not os.path.exists(so):
-        raise AmmsbError("%s not found: build it with `make -C mcmc-ammsb-gpu_amd/csrc` "
-                         "(or __graft_entry__.build()); there is no CPU fallback" % so)
-    # One HIP runtime per process: torch carries its own libamdhip64, and device pointers / streams are
-    # handed from torch to this library.  Loading torch first makes the library bind to that copy; the
-    # other order gives two runtimes that cannot see each other's devices.
-    import torch  # noqa: F401
-    lib = C.CDLL(so)
-    for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
-        fn.argtypes = args
-        fn.restype = _OTHER_RES.get(name, C.c_int)
+    lib = bind_library(path or LIB_PATH, {n: (_OTHER_RES.get(n, C.c_int), a) for n, a in SIGNATURES.items()},
+                       "; there is no CPU fallback")
     if path is None:
         _lib = lib
     return lib

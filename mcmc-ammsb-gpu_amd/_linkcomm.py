@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from ._capi import AmmsbError, Rpm
+from ._capi import AmmsbError, Rpm, bind_library, raise_for
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMMSB_LINKCOMM_LIB") or os.path.join(_HERE, "libammsb_linkcomm.so")
@@ -33,26 +33,15 @@ _lib = None
 
 
 def load():
-    """dlopen the library and bind every symbol include/ammsb_linkcomm.h declares.  A missing library is an error:
-    there is no other implementation of this read-out."""
+    """dlopen the library and bind every symbol include/ammsb_linkcomm.h declares"""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise AmmsbError("%s not found: build it with `make -C mcmc-ammsb-gpu_amd/csrc` "
-                         "(or __graft_entry__.build())" % LIB_PATH)
-    import torch  # noqa: F401  (one HIP runtime per process: see _capi.load)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = bind_library(LIB_PATH, SIGNATURES)
+    return _lib
 
 
 def check(rc):
-    if rc != 0:
-        raise AmmsbError("ammsb_linkcomm call failed: %d (%s)" % (rc, load().ammsb_linkcomm_last_error().decode()))
+    raise_for(rc, "ammsb_linkcomm", load().ammsb_linkcomm_last_error)
 
 
 def last_kernel_name():

@@ -4,7 +4,7 @@ own: _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
 import os
 
-from ._capi import AmmsbError, SetDesc
+from ._capi import AmmsbError, SetDesc, bind_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMMSB_REFSAMPLE_LIB") or os.path.join(_HERE, "libammsb_refsample.so")
@@ -39,21 +39,11 @@ _lib = None
 
 
 def load():
-    """dlopen the library and bind every symbol include/ammsb_refsample.h declares.  A missing library is an error:
-    there is no other implementation of this mode."""
+    """dlopen the library and bind every symbol include/ammsb_refsample.h declares"""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise AmmsbError("%s not found: build it with `make -C mcmc-ammsb-gpu_amd/csrc` "
-                         "(or __graft_entry__.build())" % LIB_PATH)
-    import torch  # noqa: F401  (one HIP runtime per process: see _capi.load)
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = bind_library(LIB_PATH, SIGNATURES)
+    return _lib
 
 
 def rand_r(state):

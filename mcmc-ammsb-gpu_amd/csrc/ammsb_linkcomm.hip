@@ -23,9 +23,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/ammsb_linkcomm.h"
+#include "ammsb_postfit.h"
 
 namespace {
 
@@ -33,19 +33,7 @@ typedef unsigned long long u64;
 
 constexpr int LC_WAVES = 4;  // waves (= edges in flight) per block
 constexpr int LC_BLOCK = 64 * LC_WAVES;
-constexpr int LC_MAX_GRID = 2048;  // 256 CUs x 8 blocks: past residency a block would only queue
 constexpr uint32_t NONE = AMMSB_LINKCOMM_NONE;
-
-thread_local const char* g_last_kernel = "";
-thread_local char g_last_error[256] = "";
-
-// TTRowPartitionedMatrix_Row with 64-bit offsets (rpm_row() of ammsb_dev.h): 32-bit block index, 64-bit element offset
-__device__ __forceinline__ const float* lc_row(const ammsb_rpm& m, uint32_t row) {
-  if (m.num_blocks == 1) return reinterpret_cast<const float*>(m.blocks[0]) + (uint64_t)row * m.num_cols;
-  const uint32_t rib = (uint32_t)m.rows_in_block;
-  const uint32_t blk = row / rib;
-  return reinterpret_cast<const float*>(m.blocks[blk]) + (uint64_t)(row - blk * rib) * m.num_cols;
-}
 
 struct Args {
   ammsb_rpm pi;
@@ -61,29 +49,6 @@ struct Args {
   u64* sizes;
 };
 
-// ------------------------------------------------------------------------------------------ wave reductions
-// Every lane ends with the maximum (csrc/ammsb_readout.hip): lanes of a row of 16 by DPP, rows by two shuffles.  All 64
-// lanes are active wherever this is called (control flow around it is wave-uniform).
-template <int CTRL>
-__device__ __forceinline__ int dpp(int v) {
-  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-  v = max(v, dpp<0xB1>(v));   // quad_perm [1,0,3,2]
-  v = max(v, dpp<0x4E>(v));   // quad_perm [2,3,0,1]
-  v = max(v, dpp<0x141>(v));  // row_half_mirror
-  v = max(v, dpp<0x140>(v));  // row_mirror
-  v = max(v, __shfl_xor(v, 16, 64));
-  v = max(v, __shfl_xor(v, 32, 64));
-  return v;
-}
-
-struct Best {
-  int bits;  // term bits of the lane's best eligible element; -1: none
-  uint32_t col;
-};
-
 // The term of one column as a key half: its bits if it may take a slot, else -1.  Two multiplications in this order
 // (-ffp-contract=off: no FMA); a NaN fails both comparisons.
 __device__ __forceinline__ int term_bits(float q, float bk, float min_term) {
@@ -91,26 +56,11 @@ __device__ __forceinline__ int term_bits(float q, float bk, float min_term) {
   return (t > 0.0f && t >= min_term) ? __float_as_int(t) : -1;
 }
 
-// one element offered to a lane's running best, in ascending column order (strict >: the lower column wins in a lane)
-template <bool FIRST>
-__device__ __forceinline__ void offer(Best& b, int bits, uint32_t col, int pbits, uint32_t pcol) {
-  const bool elig = FIRST || bits < pbits || (bits == pbits && col > pcol);
-  if (elig && bits > b.bits) {
-    b.bits = bits;
-    b.col = col;
-  }
-}
-
 // The winner of a round among the lanes' bests: false when nothing is left.
 __device__ __forceinline__ bool round_winner(const Best& b, int& wbits, uint32_t& wcol) {
   wbits = wave_max_i32(b.bits);
   if (wbits < 0) return false;
-  const uint64_t holders = __ballot(b.bits == wbits);
-  if (__popcll(holders) == 1) {
-    wcol = (uint32_t)__builtin_amdgcn_readlane((int)b.col, (int)__builtin_ctzll(holders));
-  } else {  // the same bits in several lanes: the lowest column (columns are < 2^31, so ~col orders as an int)
-    wcol = ~(uint32_t)wave_max_i32((int)~(b.bits == wbits ? b.col : 0x7FFFFFFFu));
-  }
+  wcol = winner_col(b, wbits);
   return true;
 }
 
@@ -137,8 +87,7 @@ __device__ __forceinline__ void select(Scan&& scan, uint32_t T, int lane, int& l
 // What a wave leaves behind for edge p: lane t holds slot t, `sum` is the lane's share of sum_k q_k w_k.
 __device__ __forceinline__ void finish(const Args& a, uint64_t p, bool ok, int lbits, uint32_t lcol, float sum, int lane,
                                        uint32_t* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  sum = wave_sum_f32(sum);
   if (a.ids && lane < (int)a.T) {
     a.ids[p * a.T + lane] = lcol;
     a.terms[p * a.T + lane] = lbits < 0 ? 0.0f : __int_as_float(lbits);
@@ -149,25 +98,16 @@ __device__ __forceinline__ void finish(const Args& a, uint64_t p, bool ok, int l
   }
 }
 
-__device__ __forceinline__ void zero_counters(const Args& a, uint32_t* lds) {
-  if (!a.sizes) return;
-  for (uint32_t s = threadIdx.x; s <= a.pi.num_cols; s += LC_BLOCK) lds[s] = 0;
-  __syncthreads();
+// the block's counters: lds[0..K], one per community and lds[K] for "no community"
+__device__ __forceinline__ void zero_sizes(const Args& a, uint32_t* lds) {
+  if (a.sizes) zero_counters<LC_BLOCK>(lds, Through{a.pi.num_cols});
 }
 
-// block-private counters -> sizes[]: one vector atomic per non-zero counter
-__device__ __forceinline__ void flush_counters(const Args& a, const uint32_t* lds) {
-  if (!a.sizes) return;
-  __syncthreads();
-  for (uint32_t s = threadIdx.x; s <= a.pi.num_cols; s += LC_BLOCK) {
-    const uint32_t c = lds[s];
-    if (c) atomicAdd(&a.sizes[s], (u64)c);
-  }
+__device__ __forceinline__ void flush_sizes(const Args& a, const uint32_t* lds) {
+  if (a.sizes) flush_counters<LC_BLOCK>(lds, Through{a.pi.num_cols}, a.sizes);
 }
 
 // ------------------------------------------------------------------------------------------ fast form
-__device__ __forceinline__ float comp(const float4& q, int c) { return c == 0 ? q.x : c == 1 ? q.y : c == 2 ? q.z : q.w; }
-
 template <int NV>
 struct Rows {
   bool ok;               // both ends < num_rows
@@ -196,8 +136,8 @@ __device__ __forceinline__ void head(const Args& a, uint64_t p, int lane, int nv
   const u64 e = a.edges[p];
   const uint32_t u = (uint32_t)(e >> 32), v = (uint32_t)e, rows = (uint32_t)a.pi.num_rows;
   r.ok = u < rows && v < rows;
-  r.pa = reinterpret_cast<const float4*>(lc_row(a.pi, r.ok ? u : 0u)) + lane;
-  r.pb = reinterpret_cast<const float4*>(lc_row(a.pi, r.ok ? v : 0u)) + lane;
+  r.pa = reinterpret_cast<const float4*>(postfit_row(a.pi, r.ok ? u : 0u)) + lane;
+  r.pb = reinterpret_cast<const float4*>(postfit_row(a.pi, r.ok ? v : 0u)) + lane;
   load_chunk<NV>(r, 0, nv);
 }
 
@@ -209,7 +149,7 @@ __global__ __launch_bounds__(LC_BLOCK) void linkcomm_fast(Args a) {
   const uint32_t K = (uint32_t)a.pi.num_cols;
   const int nvK = (int)(K >> 8);
   const int nch = CHUNKED ? (nvK + NV - 1) / NV : 1;
-  zero_counters(a, lds);
+  zero_sizes(a, lds);
   float bw[CHUNKED ? 1 : NE];  // one chunk: beta of the lane's columns, for every edge
   if constexpr (!CHUNKED) {
 #pragma unroll
@@ -274,7 +214,7 @@ __global__ __launch_bounds__(LC_BLOCK) void linkcomm_fast(Args a) {
     }
     finish(a, p, ok, lbits, lcol, sum, lane, lds);
   }
-  flush_counters(a, lds);
+  flush_sizes(a, lds);
 }
 
 // ------------------------------------------------------------------------------------------ generic form
@@ -282,14 +222,14 @@ __global__ __launch_bounds__(LC_BLOCK) void linkcomm_generic(Args a) {
   extern __shared__ uint32_t lds[];
   const int lane = threadIdx.x & 63;
   const uint32_t K = (uint32_t)a.pi.num_cols, rows = (uint32_t)a.pi.num_rows;
-  zero_counters(a, lds);
+  zero_sizes(a, lds);
   const uint64_t stride = (uint64_t)gridDim.x * LC_WAVES;
   for (uint64_t p = (uint64_t)blockIdx.x * LC_WAVES + (threadIdx.x >> 6); p < a.n; p += stride) {
     const u64 e = a.edges[p];
     const uint32_t u = (uint32_t)(e >> 32), v = (uint32_t)e;
     const bool ok = u < rows && v < rows;
-    const float* pa = lc_row(a.pi, ok ? u : 0u);
-    const float* pb = lc_row(a.pi, ok ? v : 0u);
+    const float* pa = postfit_row(a.pi, ok ? u : 0u);
+    const float* pb = postfit_row(a.pi, ok ? v : 0u);
     const uint32_t k_end = ok ? K : 0u;
     float sum = 0.0f;
     auto scan = [&](bool first, int pbits, uint32_t pcol) {
@@ -312,12 +252,7 @@ __global__ __launch_bounds__(LC_BLOCK) void linkcomm_generic(Args a) {
     select(scan, a.T, lane, lbits, lcol);
     finish(a, p, ok, lbits, lcol, sum, lane, lds);
   }
-  flush_counters(a, lds);
-}
-
-int fail(int code, const char* what) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s", what);
-  return code;
+  flush_sizes(a, lds);
 }
 
 }  // namespace
@@ -337,19 +272,8 @@ extern "C" int ammsb_linkcomm_edges(const ammsb_rpm* pi, const float* beta, floa
   if (!(min_term >= 0.0f && min_term < INFINITY)) return fail(AMMSB_EINVAL, "min_term negative, NaN or infinite");
   if (!(epsilon >= 0.0f && epsilon < 1.0f)) return fail(AMMSB_EINVAL, "epsilon outside [0, 1)");
   bool aligned = true;
-  if (pi) {
-    const uint64_t K = pi->num_cols;
-    if (K == 0 || K > AMMSB_LINKCOMM_MAX_COLS) return fail(AMMSB_EINVAL, "num_cols outside 1..8192");
-    if (pi->num_rows >> 32) return fail(AMMSB_EINVAL, "2^32 rows or more");
-    if (pi->num_blocks == 0 || pi->num_blocks > AMMSB_RPM_MAX_BLOCKS || pi->rows_in_block == 0 ||
-        pi->rows_in_block >> 32 || pi->rows_in_block * pi->num_blocks < pi->num_rows ||
-        (pi->num_rows && (pi->num_rows - 1) / pi->rows_in_block >= pi->num_blocks))
-      return fail(AMMSB_EINVAL, "the blocks do not cover num_rows");
-    for (uint32_t b = 0; b < pi->num_blocks; ++b) {
-      if (!pi->blocks[b]) return fail(AMMSB_EINVAL, "a block pointer is NULL");
-      aligned = aligned && (reinterpret_cast<uintptr_t>(pi->blocks[b]) & 15) == 0;
-    }
-  }
+  if (pi)
+    if (const char* bad = check_rpm(pi, AMMSB_LINKCOMM_MAX_COLS, &aligned)) return fail(AMMSB_EINVAL, bad);
   if (n == 0) return AMMSB_OK;
 
   Args a;
@@ -365,8 +289,7 @@ extern "C" int ammsb_linkcomm_edges(const ammsb_rpm* pi, const float* beta, floa
   a.prob = prob;
   a.sizes = reinterpret_cast<u64*>(sizes);
   const uint64_t K = pi->num_cols;
-  const uint64_t want = (n + LC_WAVES - 1) / LC_WAVES;
-  const dim3 grid((unsigned)(want < (uint64_t)LC_MAX_GRID ? want : (uint64_t)LC_MAX_GRID)), block(LC_BLOCK);
+  const dim3 grid(persistent_grid(n, LC_WAVES)), block(LC_BLOCK);
   const size_t lds = sizes ? (size_t)(K + 1) * sizeof(uint32_t) : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const char* name;
@@ -380,11 +303,5 @@ extern "C" int ammsb_linkcomm_edges(const ammsb_rpm* pi, const float* beta, floa
     name = "linkcomm_generic";
     hipLaunchKernelGGL(linkcomm_generic, grid, block, lds, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_last_error, sizeof(g_last_error), "%s: %s", name, hipGetErrorString(e));
-    return AMMSB_EHIP;
-  }
-  g_last_kernel = name;
-  return AMMSB_OK;
+  return launched(name);
 }

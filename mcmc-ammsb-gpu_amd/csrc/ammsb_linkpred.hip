@@ -23,10 +23,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/ammsb_linkpred.h"
 #include "ammsb_dev.h"  // set_has(DevSet): the one copy of the cuckoo hash pair, with the fast_mod magic
+#include "ammsb_postfit.h"
 
 namespace {
 
@@ -40,19 +40,7 @@ constexpr int LP_BLOCK = 256;        // 4 waves
 constexpr int KC = 32;               // columns per chunk
 constexpr int LDW = 36;              // LDS row stride in words: 16-byte aligned rows, 16 lanes x float4 hit 64 banks once
 constexpr uint32_t NONE = AMMSB_LINKPRED_NONE;
-constexpr uint32_t TARGET_GRID = 2048;  // 256 CUs x 8: what a persistent `top` grid aims for
-constexpr int PAIR_MAX_GRID = 2048;
-
-thread_local const char* g_last_kernel = "";
-thread_local char g_last_error[256] = "";
-
-// TTRowPartitionedMatrix_Row with 64-bit offsets (rpm_row() of ammsb_dev.h)
-__device__ __forceinline__ const float* lp_row(const ammsb_rpm& m, uint32_t row) {
-  if (m.num_blocks == 1) return reinterpret_cast<const float*>(m.blocks[0]) + (uint64_t)row * m.num_cols;
-  const uint32_t rib = (uint32_t)m.rows_in_block;
-  const uint32_t blk = row / rib;
-  return reinterpret_cast<const float*>(m.blocks[blk]) + (uint64_t)(row - blk * rib) * m.num_cols;
-}
+constexpr uint32_t TARGET_GRID = MAX_GRID;  // what a persistent `top` grid aims for
 
 // Is edge e in one of the exclusion sets?  Out of line: reached by the few candidates that pass a list's bar, and the
 // epilogue's unrolled register loop stays small.
@@ -167,7 +155,7 @@ __global__ __launch_bounds__(LP_BLOCK) void linkpred_tile(TileArgs a) {
 #pragma unroll
   for (int p = 0; p < PA; ++p) {
     const uint32_t q = qid[p * 32 + r0];
-    pa[p] = q == NONE ? nullptr : lp_row(a.pi, q);
+    pa[p] = q == NONE ? nullptr : postfit_row(a.pi, q);
   }
   const uint32_t nch = (K + KC - 1) / KC;
   const uint32_t tile_end = min(a.tiles, (part + 1) * a.tiles_per_part);
@@ -177,7 +165,7 @@ __global__ __launch_bounds__(LP_BLOCK) void linkpred_tile(TileArgs a) {
 #pragma unroll
     for (int p = 0; p < PB; ++p) {
       const uint32_t j = tile * TC + p * 32 + r0;
-      pb[p] = j < a.cand_n ? lp_row(a.pi, a.cand_lo + j) : nullptr;
+      pb[p] = j < a.cand_n ? postfit_row(a.pi, a.cand_lo + j) : nullptr;
     }
     f32x16 acc[2];
 #pragma unroll
@@ -322,8 +310,8 @@ __device__ __forceinline__ PairHead pair_head(const PairArgs& a, uint64_t p, uin
   const uint32_t u = (uint32_t)(e >> 32), v = (uint32_t)e, rows = (uint32_t)a.pi.num_rows;
   PairHead hd;
   const bool ok = u < rows && v < rows;
-  hd.pa = ok ? lp_row(a.pi, u) : nullptr;
-  hd.pb = ok ? lp_row(a.pi, v) : nullptr;
+  hd.pa = ok ? postfit_row(a.pi, u) : nullptr;
+  hd.pb = ok ? postfit_row(a.pi, v) : nullptr;
   if constexpr (VEC) {
     hd.x = load4<true>(hd.pa, 4 * lane, (uint32_t)a.pi.num_cols);
     hd.y = load4<true>(hd.pb, 4 * lane, (uint32_t)a.pi.num_cols);
@@ -359,6 +347,7 @@ __global__ __launch_bounds__(LP_BLOCK) void linkpred_pairs(PairArgs a) {
         for (uint32_t k = lane; k < K; k += 64) sum += (cur.pa[k] * (a.beta[2 * k + 1] - a.eps)) * cur.pb[k];
       }
     }
+    // wave_sum_f32() written out: through the helper the kernel's prologue is scheduled in another order
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (lane == 0) a.out[p] = cur.pa ? sum + a.eps : -1.0f;
@@ -366,29 +355,14 @@ __global__ __launch_bounds__(LP_BLOCK) void linkpred_pairs(PairArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-int fail(int code, const char* what) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s", what);
-  return code;
-}
-
 // the checks every entry shares; *vec: 16-byte loads are possible
 int check_model(const ammsb_rpm* pi, const float* beta, float eps, bool* vec) {
   if (!pi) return fail(AMMSB_EINVAL, "pi is NULL");
   if (!beta) return fail(AMMSB_EINVAL, "beta is NULL");
   if (!(eps >= 0.0f && eps < 1.0f)) return fail(AMMSB_EINVAL, "epsilon outside [0, 1)");
-  const uint64_t K = pi->num_cols;
-  if (K == 0 || K > AMMSB_LINKPRED_MAX_COLS) return fail(AMMSB_EINVAL, "num_cols outside 1..8192");
-  if (pi->num_rows >> 32) return fail(AMMSB_EINVAL, "2^32 rows or more");
-  if (pi->num_blocks == 0 || pi->num_blocks > AMMSB_RPM_MAX_BLOCKS || pi->rows_in_block == 0 ||
-      pi->rows_in_block >> 32 || pi->rows_in_block * pi->num_blocks < pi->num_rows ||
-      (pi->num_rows && (pi->num_rows - 1) / pi->rows_in_block >= pi->num_blocks))
-    return fail(AMMSB_EINVAL, "the blocks do not cover num_rows");
-  bool aligned = K % 4 == 0;
-  for (uint32_t b = 0; b < pi->num_blocks; ++b) {
-    if (!pi->blocks[b]) return fail(AMMSB_EINVAL, "a block pointer is NULL");
-    aligned = aligned && (reinterpret_cast<uintptr_t>(pi->blocks[b]) & 15) == 0;
-  }
-  *vec = aligned;
+  bool aligned;
+  if (const char* bad = check_rpm(pi, AMMSB_LINKPRED_MAX_COLS, &aligned)) return fail(AMMSB_EINVAL, bad);
+  *vec = aligned && pi->num_cols % 4 == 0;
   return AMMSB_OK;
 }
 
@@ -447,11 +421,6 @@ const char* launch_tile(const Plan& p, bool vec, const TileArgs& a, size_t lds, 
   }
 #undef LP_LAUNCH
   return name;
-}
-
-int hip_fail(const char* name, hipError_t e) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s: %s", name, hipGetErrorString(e));
-  return AMMSB_EHIP;
 }
 
 }  // namespace
@@ -537,7 +506,7 @@ extern "C" int ammsb_linkpred_top(const ammsb_rpm* pi, const float* beta, float 
   hipLaunchKernelGGL(linkpred_merge, dim3(Q), dim3(64), 0, s, a.ws, p.L, T, ids, scores);
   e = hipGetLastError();
   if (e != hipSuccess) return hip_fail("linkpred_merge", e);
-  g_last_kernel = name;
+  g_last_kernel = name;  // the tile form, not the merge
   return AMMSB_OK;
 }
 
@@ -550,8 +519,7 @@ extern "C" int ammsb_linkpred_pairs(const ammsb_rpm* pi, const float* beta, floa
   if (!out) return fail(AMMSB_EINVAL, "out is NULL");
   if (n == 0) return AMMSB_OK;
   PairArgs a = {*pi, beta, epsilon, reinterpret_cast<const u64*>(edges), n, out};
-  const uint64_t want = (n + LP_BLOCK / 64 - 1) / (LP_BLOCK / 64);
-  const dim3 grid((unsigned)(want < (uint64_t)PAIR_MAX_GRID ? want : (uint64_t)PAIR_MAX_GRID)), block(LP_BLOCK);
+  const dim3 grid(persistent_grid(n, LP_BLOCK / 64)), block(LP_BLOCK);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const char* name;
   if (vec) {
@@ -561,8 +529,5 @@ extern "C" int ammsb_linkpred_pairs(const ammsb_rpm* pi, const float* beta, floa
     name = "linkpred_pairs_v1";
     hipLaunchKernelGGL(linkpred_pairs<false>, grid, block, 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(name, e);
-  g_last_kernel = name;
-  return AMMSB_OK;
+  return launched(name);
 }

@@ -17,9 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/ammsb_quality.h"
+#include "ammsb_postfit.h"
 
 namespace {
 
@@ -27,19 +27,7 @@ typedef unsigned long long u64;
 
 constexpr int Q_WAVES = 4;  // waves per block
 constexpr int Q_BLOCK = 64 * Q_WAVES;
-constexpr int Q_MAX_GRID = 2048;  // 256 CUs x 8 blocks: past residency a block would only queue
 constexpr int Q_TRIPS = 4;  // edges a group takes before another block is worth its 2 K + 2 counters' zeroing and flush
-
-thread_local const char* g_last_kernel = "";
-thread_local char g_last_error[256] = "";
-
-// TTRowPartitionedMatrix_Row with 64-bit offsets (rpm_row() of ammsb_dev.h): 32-bit block index, 64-bit element offset
-__device__ __forceinline__ const float* q_row(const ammsb_rpm& m, uint32_t row) {
-  if (m.num_blocks == 1) return reinterpret_cast<const float*>(m.blocks[0]) + (uint64_t)row * m.num_cols;
-  const uint32_t rib = (uint32_t)m.rows_in_block;
-  const uint32_t blk = row / rib;
-  return reinterpret_cast<const float*>(m.blocks[blk]) + (uint64_t)(row - blk * rib) * m.num_cols;
-}
 
 // ------------------------------------------------------------------------------------------ the mask pass
 struct MaskArgs {
@@ -47,8 +35,6 @@ struct MaskArgs {
   float thr;
   u64* mask;
 };
-
-__device__ __forceinline__ float comp(const float4& q, int c) { return c == 0 ? q.x : c == 1 ? q.y : c == 2 ? q.z : q.w; }
 
 // word t of the row goes to lane t & 63, into its first (t < 64) or second register
 __device__ __forceinline__ void place(u64& w0, u64& w1, uint32_t t, u64 bits, int lane) {
@@ -67,7 +53,7 @@ __device__ __forceinline__ void store_row(const MaskArgs& a, uint64_t row, uint3
 // up to 4 float4 per lane: columns 1024 ch + 256 i + 4 lane + c of the row; registers past the row hold -1, which is
 // below every threshold the entry point lets through
 __device__ __forceinline__ void load_chunk(const MaskArgs& a, uint32_t row, int ch, int nvK, int lane, float4 (&x)[4]) {
-  const float4* p = reinterpret_cast<const float4*>(q_row(a.pi, row)) + ch * 256 + lane;
+  const float4* p = reinterpret_cast<const float4*>(postfit_row(a.pi, row)) + ch * 256 + lane;
   const int nv = min(nvK - 4 * ch, 4);
   const float4 none = {-1.f, -1.f, -1.f, -1.f};
 #pragma unroll
@@ -106,7 +92,7 @@ __global__ __launch_bounds__(Q_BLOCK) void quality_mask_generic(MaskArgs a) {
   const uint32_t K = (uint32_t)a.pi.num_cols, W = (K + 63u) >> 6, F = 4u * (K >> 8);
   const uint64_t rows = a.pi.num_rows, stride = (uint64_t)gridDim.x * Q_WAVES;
   for (uint64_t r = (uint64_t)blockIdx.x * Q_WAVES + (threadIdx.x >> 6); r < rows; r += stride) {
-    const float* p = q_row(a.pi, (uint32_t)r);
+    const float* p = postfit_row(a.pi, (uint32_t)r);
     u64 w0 = 0, w1 = 0;
     for (uint32_t t = 0; t < W; ++t) {
       const uint32_t col = t < F ? 256u * (t >> 2) + 4u * lane + (t & 3u) : 64u * t + lane;
@@ -175,10 +161,7 @@ __device__ __forceinline__ void edges_body(const EdgeArgs& a, uint32_t* lds) {
   const uint32_t K = a.K, F = 4u * (K >> 8), ncnt = 2u * K + 2u;
   const uint32_t gshift = WPL == 1 ? a.gshift : 6u, G = 1u << gshift;
   const uint32_t gl = lane & (G - 1u), slot = lane >> gshift, epw = 64u >> gshift;
-  if (a.counts) {
-    for (uint32_t s = threadIdx.x; s < ncnt; s += Q_BLOCK) lds[s] = 0;
-    __syncthreads();
-  }
+  if (a.counts) zero_counters<Q_BLOCK>(lds, ncnt);
   const uint64_t stride = (uint64_t)gridDim.x * Q_WAVES * epw;
   uint64_t pb = ((uint64_t)blockIdx.x * Q_WAVES + (threadIdx.x >> 6)) * epw;  // the wave's first edge: wave-uniform
   Ends<WPL> e;
@@ -214,13 +197,7 @@ __device__ __forceinline__ void edges_body(const EdgeArgs& a, uint32_t* lds) {
       }
     }
   }
-  if (a.counts) {  // block-private counters -> counts[]: one vector atomic per non-zero counter
-    __syncthreads();
-    for (uint32_t s = threadIdx.x; s < ncnt; s += Q_BLOCK) {
-      const uint32_t c = lds[s];
-      if (c) atomicAdd(&a.counts[s], (u64)c);
-    }
-  }
+  if (a.counts) flush_counters<Q_BLOCK>(lds, ncnt, a.counts);
 }
 
 // WPL words per lane: 1 while a row's words fit a wave (K <= 4096), 2 above
@@ -232,21 +209,6 @@ __global__ __launch_bounds__(Q_BLOCK) void quality_edges_w1(EdgeArgs a) {
 __global__ __launch_bounds__(Q_BLOCK) void quality_edges_w2(EdgeArgs a) {
   extern __shared__ uint32_t lds[];
   edges_body<2>(a, lds);
-}
-
-int fail(int code, const char* what) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s", what);
-  return code;
-}
-
-int launched(const char* name) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_last_error, sizeof(g_last_error), "%s: %s", name, hipGetErrorString(e));
-    return AMMSB_EHIP;
-  }
-  g_last_kernel = name;
-  return AMMSB_OK;
 }
 
 bool shape_ok(uint64_t num_rows, uint64_t num_cols) {
@@ -267,18 +229,8 @@ extern "C" int ammsb_quality_mask(const ammsb_rpm* pi, float thr, uint64_t* mask
   if (!pi) return fail(AMMSB_EINVAL, "pi is NULL");
   if (!mask) return fail(AMMSB_EINVAL, "mask is NULL");
   if (!(thr >= 0.0f && thr < INFINITY)) return fail(AMMSB_EINVAL, "thr negative, NaN or infinite");
-  const uint64_t K = pi->num_cols;
-  if (K == 0 || K > AMMSB_QUALITY_MAX_COLS) return fail(AMMSB_EINVAL, "num_cols outside 1..8192");
-  if (pi->num_rows >> 32) return fail(AMMSB_EINVAL, "2^32 rows or more");
-  if (pi->num_blocks == 0 || pi->num_blocks > AMMSB_RPM_MAX_BLOCKS || pi->rows_in_block == 0 ||
-      pi->rows_in_block >> 32 || pi->rows_in_block * pi->num_blocks < pi->num_rows ||
-      (pi->num_rows && (pi->num_rows - 1) / pi->rows_in_block >= pi->num_blocks))
-    return fail(AMMSB_EINVAL, "the blocks do not cover num_rows");
-  bool aligned = true;
-  for (uint32_t b = 0; b < pi->num_blocks; ++b) {
-    if (!pi->blocks[b]) return fail(AMMSB_EINVAL, "a block pointer is NULL");
-    aligned = aligned && (reinterpret_cast<uintptr_t>(pi->blocks[b]) & 15) == 0;
-  }
+  bool aligned;
+  if (const char* bad = check_rpm(pi, AMMSB_QUALITY_MAX_COLS, &aligned)) return fail(AMMSB_EINVAL, bad);
   if (reinterpret_cast<uintptr_t>(mask) & 7) return fail(AMMSB_EINVAL, "mask is not 8-byte aligned");
   if (pi->num_rows == 0) return AMMSB_OK;
 
@@ -286,11 +238,10 @@ extern "C" int ammsb_quality_mask(const ammsb_rpm* pi, float thr, uint64_t* mask
   a.pi = *pi;
   a.thr = thr;
   a.mask = reinterpret_cast<u64*>(mask);
-  const uint64_t want = (pi->num_rows + Q_WAVES - 1) / Q_WAVES;
-  const dim3 grid((unsigned)(want < (uint64_t)Q_MAX_GRID ? want : (uint64_t)Q_MAX_GRID)), block(Q_BLOCK);
+  const dim3 grid(persistent_grid(pi->num_rows, Q_WAVES)), block(Q_BLOCK);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const char* name;
-  if (K % 256 == 0 && aligned) {
+  if (pi->num_cols % 256 == 0 && aligned) {
     name = "quality_mask_fast";
     hipLaunchKernelGGL(quality_mask_fast, grid, block, 0, s, a);
   } else {
@@ -320,9 +271,7 @@ extern "C" int ammsb_quality_edges(const uint64_t* mask, uint64_t num_rows, uint
   a.n = n;
   a.counts = reinterpret_cast<u64*>(counts);
   a.shared = shared;
-  const uint64_t per_block = (uint64_t)Q_WAVES * (64u >> a.gshift) * Q_TRIPS;
-  const uint64_t want = (n + per_block - 1) / per_block;
-  const dim3 grid((unsigned)(want < (uint64_t)Q_MAX_GRID ? want : (uint64_t)Q_MAX_GRID)), block(Q_BLOCK);
+  const dim3 grid(persistent_grid(n, (uint64_t)Q_WAVES * (64u >> a.gshift) * Q_TRIPS)), block(Q_BLOCK);
   const size_t lds = counts ? (size_t)(2u * num_cols + 2u) * sizeof(uint32_t) : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const char* name;
@@ -335,10 +284,7 @@ extern "C" int ammsb_quality_edges(const uint64_t* mask, uint64_t num_rows, uint
     static const hipError_t big =
         hipFuncSetAttribute(reinterpret_cast<const void*>(&quality_edges_w2), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)((2u * AMMSB_QUALITY_MAX_COLS + 2u) * sizeof(uint32_t)));
-    if (big != hipSuccess) {
-      snprintf(g_last_error, sizeof(g_last_error), "%s: %s", name, hipGetErrorString(big));
-      return AMMSB_EHIP;
-    }
+    if (big != hipSuccess) return hip_fail(name, big);
     hipLaunchKernelGGL(quality_edges_w2, grid, block, lds, s, a);
   }
   return launched(name);

@@ -15,73 +15,21 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/ammsb_readout.h"
+#include "ammsb_postfit.h"
 
 namespace {
 
 constexpr int RO_WAVES = 4;               // waves (= rows in flight) per block
 constexpr int RO_BLOCK = 64 * RO_WAVES;
-constexpr int RO_MAX_GRID = 2048;         // 256 CUs x 8 blocks: past residency a block would only queue
 constexpr uint32_t NONE = AMMSB_READOUT_NONE;
-
-thread_local const char* g_last_kernel = "";
-thread_local char g_last_error[256] = "";
-
-// TTRowPartitionedMatrix_Row with 64-bit offsets (the few lines of rpm_row() in ammsb_dev.h: row indices are vertex
-// ids, so the block index is a 32-bit division; the element offset is 64-bit)
-__device__ __forceinline__ const float* ro_row(const ammsb_rpm& m, uint32_t row) {
-  if (m.num_blocks == 1) return reinterpret_cast<const float*>(m.blocks[0]) + (uint64_t)row * m.num_cols;
-  const uint32_t rib = (uint32_t)m.rows_in_block;
-  const uint32_t blk = row / rib;
-  return reinterpret_cast<const float*>(m.blocks[blk]) + (uint64_t)(row - blk * rib) * m.num_cols;
-}
-
-// ------------------------------------------------------------------------------------------ wave reductions
-// Every lane ends with the maximum.  Lanes 0..15 of each row of 16 by DPP (two quad permutes, then the mirrors pair
-// quads and halves: a max does not care which partner it meets, only that the groups merge), rows by two shuffles.
-// All 64 lanes are active wherever this is called (control flow around it is wave-uniform).
-template <int CTRL>
-__device__ __forceinline__ int dpp(int v) {
-  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-  v = max(v, dpp<0xB1>(v));   // quad_perm [1,0,3,2]
-  v = max(v, dpp<0x4E>(v));   // quad_perm [2,3,0,1]
-  v = max(v, dpp<0x141>(v));  // row_half_mirror
-  v = max(v, dpp<0x140>(v));  // row_mirror
-  v = max(v, __shfl_xor(v, 16, 64));
-  v = max(v, __shfl_xor(v, 32, 64));
-  return v;
-}
-
-struct Best {
-  int bits;      // value bits of the lane's best eligible element; -1: none
-  uint32_t col;
-};
-
-// one element offered to a lane's running best, in ascending column order
-template <bool FIRST>
-__device__ __forceinline__ void offer(Best& b, int bits, uint32_t col, int pbits, uint32_t pcol) {
-  const bool elig = FIRST || bits < pbits || (bits == pbits && col > pcol);
-  if (elig && bits > b.bits) {
-    b.bits = bits;
-    b.col = col;
-  }
-}
 
 // The winner of a round among the lanes' bests: false when nothing is left or the maximum is below the threshold.
 __device__ __forceinline__ bool round_winner(const Best& b, float thr, int& wbits, uint32_t& wcol) {
   wbits = wave_max_i32(b.bits);
   if (wbits < 0 || __int_as_float(wbits) < thr) return false;
-  const uint64_t holders = __ballot(b.bits == wbits);
-  if (__popcll(holders) == 1) {
-    wcol = (uint32_t)__builtin_amdgcn_readlane((int)b.col, (int)__builtin_ctzll(holders));
-  } else {  // the same value in several lanes: the lowest column (columns are < 2^31, so ~col orders as an int)
-    wcol = ~(uint32_t)wave_max_i32((int)~(b.bits == wbits ? b.col : 0x7FFFFFFFu));
-  }
+  wcol = winner_col(b, wbits);
   return true;
 }
 
@@ -120,16 +68,6 @@ __device__ __forceinline__ void select_row(Scan&& scan, uint64_t r, const Out& o
   if (lane == 0) o.count[r] = cnt;
 }
 
-// block-private size counters -> sizes[]: one vector atomic per non-zero counter
-template <class ColOf>
-__device__ __forceinline__ void flush_sizes(const uint32_t* lds, uint32_t slots, unsigned long long* sizes, ColOf&& col_of) {
-  __syncthreads();
-  for (uint32_t s = threadIdx.x; s < slots; s += RO_BLOCK) {
-    const uint32_t c = lds[s];
-    if (c) atomicAdd(&sizes[col_of(s)], (unsigned long long)c);
-  }
-}
-
 struct Args {
   ammsb_rpm pi;
   const uint32_t* nodes;
@@ -143,20 +81,24 @@ struct Args {
 // K = 256 nv, nv <= NV: lane l holds columns 256 i + 4 l + c (i < nv, c < 4) as NV float4 registers; registers past nv
 // hold bit pattern -1 (a NaN as a float: never >= thr; as an int below every value: never selected).  The size counter
 // of register slot j = 4 i + c of lane l is lds[64 j + l]: a wave's ds_add touches 64 consecutive words.
-__device__ __forceinline__ float comp(const float4& q, int c) { return c == 0 ? q.x : c == 1 ? q.y : c == 2 ? q.z : q.w; }
-
 template <int NV>
 __device__ __forceinline__ void load_row(const Args& a, uint64_t r, int nv, int lane, uint32_t num_rows, float4 (&v)[NV],
                                          bool& ok) {
   const uint32_t row = a.nodes ? a.nodes[r] : (uint32_t)(a.row_lo + r);
   ok = row < num_rows;
   const float4 none = {__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), __int_as_float(-1)};
-  const float4* p = reinterpret_cast<const float4*>(ro_row(a.pi, ok ? row : 0u)) + lane;
+  const float4* p = reinterpret_cast<const float4*>(postfit_row(a.pi, ok ? row : 0u)) + lane;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     v[i] = none;
     if (ok && i < nv) v[i] = p[i * 64];
   }
+}
+
+// the column whose size counter is lds[s]
+__device__ __forceinline__ uint32_t fast_col_of(uint32_t s) {
+  const uint32_t j = s >> 6, l = s & 63;
+  return 256 * (j >> 2) + 4 * l + (j & 3);
 }
 
 template <int NV>
@@ -165,11 +107,9 @@ __global__ __launch_bounds__(RO_BLOCK) void readout_fast(Args a) {
   const int lane = threadIdx.x & 63;
   const int nv = (int)(a.pi.num_cols >> 8);
   const uint32_t num_rows = (uint32_t)a.pi.num_rows;
-  const bool do_sizes = a.sizes != nullptr;
-  if (do_sizes) {
-    for (uint32_t s = threadIdx.x; s < a.pi.num_cols; s += RO_BLOCK) lds[s] = 0;
-    __syncthreads();
-  }
+  unsigned long long* const sizes = a.sizes;
+  const bool do_sizes = sizes != nullptr;
+  if (do_sizes) zero_counters<RO_BLOCK>(lds, a.pi.num_cols);
   const uint64_t stride = (uint64_t)gridDim.x * RO_WAVES;
   uint64_t r = (uint64_t)blockIdx.x * RO_WAVES + (threadIdx.x >> 6);
   // small rows: the next row's loads are issued before this row's rounds (the other waves of the SIMD cover the rest)
@@ -215,10 +155,7 @@ __global__ __launch_bounds__(RO_BLOCK) void readout_fast(Args a) {
     }
   }
   if (do_sizes)
-    flush_sizes(lds, (uint32_t)a.pi.num_cols, a.sizes, [](uint32_t s) {
-      const uint32_t j = s >> 6, l = s & 63;
-      return 256 * (j >> 2) + 4 * l + (j & 3);
-    });
+    flush_counters<RO_BLOCK, fast_col_of>(lds, (uint32_t)a.pi.num_cols, sizes);
 }
 
 // ------------------------------------------------------------------------------------------ generic form
@@ -229,16 +166,14 @@ __global__ __launch_bounds__(RO_BLOCK) void readout_generic(Args a) {
   const int lane = threadIdx.x & 63;
   const uint32_t K = (uint32_t)a.pi.num_cols;
   const uint32_t num_rows = (uint32_t)a.pi.num_rows;
-  const bool do_sizes = a.sizes != nullptr;
-  if (do_sizes) {
-    for (uint32_t s = threadIdx.x; s < K; s += RO_BLOCK) lds[s] = 0;
-    __syncthreads();
-  }
+  unsigned long long* const sizes = a.sizes;
+  const bool do_sizes = sizes != nullptr;
+  if (do_sizes) zero_counters<RO_BLOCK>(lds, K);
   const uint64_t stride = (uint64_t)gridDim.x * RO_WAVES;
   for (uint64_t r = (uint64_t)blockIdx.x * RO_WAVES + (threadIdx.x >> 6); r < a.n_rows; r += stride) {
     const uint32_t row = a.nodes ? a.nodes[r] : (uint32_t)(a.row_lo + r);
     const bool ok = row < num_rows;
-    const float* p = ro_row(a.pi, ok ? row : 0u);
+    const float* p = postfit_row(a.pi, ok ? row : 0u);
     const uint32_t k_end = ok ? K : 0u;
     auto scan = [&](bool first, int pbits, uint32_t pcol, uint32_t& cnt) {
       Best b = {-1, NONE};
@@ -260,12 +195,7 @@ __global__ __launch_bounds__(RO_BLOCK) void readout_generic(Args a) {
     };
     select_row(scan, r, a.out, a.thr, lane);
   }
-  if (do_sizes) flush_sizes(lds, K, a.sizes, [](uint32_t s) { return s; });
-}
-
-int fail(int code, const char* what) {
-  snprintf(g_last_error, sizeof(g_last_error), "%s", what);
-  return code;
+  if (do_sizes) flush_counters<RO_BLOCK>(lds, K, sizes);
 }
 
 }  // namespace
@@ -282,20 +212,11 @@ extern "C" int ammsb_readout_top(const ammsb_rpm* pi, const uint32_t* nodes, uin
   if (!tops && !sizes) return fail(AMMSB_EINVAL, "no output");
   if (tops && (T == 0 || T > AMMSB_READOUT_MAX_TOP)) return fail(AMMSB_EINVAL, "T outside 1..16");
   if (!(thr >= 0.0f)) return fail(AMMSB_EINVAL, "thr negative or NaN");
-  const uint64_t K = pi->num_cols;
-  if (K == 0 || K > AMMSB_READOUT_MAX_COLS) return fail(AMMSB_EINVAL, "num_cols outside 1..8192");
-  if (pi->num_rows >> 32 || n_rows >> 32) return fail(AMMSB_EINVAL, "2^32 rows or more");
+  bool aligned;
+  if (const char* bad = check_rpm(pi, AMMSB_READOUT_MAX_COLS, &aligned)) return fail(AMMSB_EINVAL, bad);
+  if (n_rows >> 32) return fail(AMMSB_EINVAL, "2^32 rows or more");
   if (nodes ? row_lo != 0 : (row_lo > pi->num_rows || n_rows > pi->num_rows - row_lo))
     return fail(AMMSB_EINVAL, nodes ? "a node list with row_lo != 0" : "row range past num_rows");
-  if (pi->num_blocks == 0 || pi->num_blocks > AMMSB_RPM_MAX_BLOCKS || pi->rows_in_block == 0 ||
-      pi->rows_in_block >> 32 || pi->rows_in_block * pi->num_blocks < pi->num_rows ||
-      (pi->num_rows && (pi->num_rows - 1) / pi->rows_in_block >= pi->num_blocks))
-    return fail(AMMSB_EINVAL, "the blocks do not cover num_rows");
-  bool aligned = true;
-  for (uint32_t b = 0; b < pi->num_blocks; ++b) {
-    if (!pi->blocks[b]) return fail(AMMSB_EINVAL, "a block pointer is NULL");
-    aligned = aligned && (reinterpret_cast<uintptr_t>(pi->blocks[b]) & 15) == 0;
-  }
   if (n_rows == 0) return AMMSB_OK;
 
   Args a;
@@ -306,8 +227,8 @@ extern "C" int ammsb_readout_top(const ammsb_rpm* pi, const uint32_t* nodes, uin
   a.thr = thr;
   a.out = {ids, weights, count, tops ? T : 0u};
   a.sizes = reinterpret_cast<unsigned long long*>(sizes);
-  const uint64_t want = (n_rows + RO_WAVES - 1) / RO_WAVES;
-  const dim3 grid((unsigned)(want < (uint64_t)RO_MAX_GRID ? want : (uint64_t)RO_MAX_GRID)), block(RO_BLOCK);
+  const uint64_t K = pi->num_cols;
+  const dim3 grid(persistent_grid(n_rows, RO_WAVES)), block(RO_BLOCK);
   const size_t lds = sizes ? (size_t)K * sizeof(uint32_t) : 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const char* name;
@@ -323,11 +244,5 @@ extern "C" int ammsb_readout_top(const ammsb_rpm* pi, const uint32_t* nodes, uin
     name = "readout_generic";
     hipLaunchKernelGGL(readout_generic, grid, block, lds, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_last_error, sizeof(g_last_error), "%s: %s", name, hipGetErrorString(e));
-    return AMMSB_EHIP;
-  }
-  g_last_kernel = name;
-  return AMMSB_OK;
+  return launched(name);
 }

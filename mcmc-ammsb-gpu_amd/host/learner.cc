@@ -34,6 +34,11 @@ namespace {
 clcuda::Buffer<Edge> Upload(const clcuda::Queue& q, const std::vector<Edge>& v) {
   return clcuda::Buffer<Edge>(q.GetContext(), q, v.begin(), v.end());
 }
+
+// what a failed call of one of the post-fit libraries throws: its return code in words and the library's own detail
+std::runtime_error PostfitError(const char* call, int rc, const char* detail) {
+  return std::runtime_error(std::string(call) + ": " + ammsb_strerror(rc) + " (" + detail + ")");
+}
 }  // namespace
 
 std::vector<Edge> MakeEdgesForTrainingPerplexity(const Config& cfg) {
@@ -1055,7 +1060,7 @@ void Learner::Memberships(uint32_t top, Float threshold, std::vector<uint32_t>* 
                                      tops ? d_weights() : nullptr, tops ? d_count() : nullptr,
                                      d_sizes ? (*d_sizes)() : nullptr, queue_.stream());
     if (rc != AMMSB_OK)
-      throw std::runtime_error(std::string("ammsb_readout_top: ") + ammsb_strerror(rc) + " (" + ammsb_readout_last_error() + ")");
+      throw PostfitError("ammsb_readout_top", rc, ammsb_readout_last_error());
     if (ids) d_ids.Read(queue_, n * top, ids->data() + lo * top);
     if (weights) d_weights.Read(queue_, n * top, weights->data() + lo * top);
     if (count) d_count.Read(queue_, n, count->data() + lo);
@@ -1110,7 +1115,7 @@ void Learner::LinkProbabilities(const std::vector<Edge>& edges, std::vector<Floa
   const int rc = ammsb_linkpred_pairs(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), edges.size(),
                                       d_out(), queue_.stream());
   if (rc != AMMSB_OK)
-    throw std::runtime_error(std::string("ammsb_linkpred_pairs: ") + ammsb_strerror(rc) + " (" + ammsb_linkpred_last_error() + ")");
+    throw PostfitError("ammsb_linkpred_pairs", rc, ammsb_linkpred_last_error());
   d_out.Read(queue_, edges.size(), out->data());
   queue_.Finish();
 }
@@ -1144,7 +1149,7 @@ void Learner::PredictLinks(const std::vector<Vertex>& nodes, uint32_t top, uint3
     const int rc = ammsb_linkpred_top(&pi_->Get(), beta_.data(), eps, d_nodes() + lo, static_cast<uint32_t>(n), top, ex[0],
                                       ex[1], 0, N, d_ids(), d_scores(), d_ws(), ws_bytes, queue_.stream());
     if (rc != AMMSB_OK)
-      throw std::runtime_error(std::string("ammsb_linkpred_top: ") + ammsb_strerror(rc) + " (" + ammsb_linkpred_last_error() + ")");
+      throw PostfitError("ammsb_linkpred_top", rc, ammsb_linkpred_last_error());
     d_ids.Read(queue_, n * top, ids->data() + lo * top);
     d_scores.Read(queue_, n * top, scores->data() + lo * top);
   }
@@ -1210,7 +1215,7 @@ void Learner::LinkCommunities(const std::vector<Edge>& edges, uint32_t top, Floa
     const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), eps, d_edges() + lo, n, top, min_term, d_ids(),
                                         d_terms(), d_prob(), nullptr, queue_.stream());
     if (rc != AMMSB_OK)
-      throw std::runtime_error(std::string("ammsb_linkcomm_edges: ") + ammsb_strerror(rc) + " (" + ammsb_linkcomm_last_error() + ")");
+      throw PostfitError("ammsb_linkcomm_edges", rc, ammsb_linkcomm_last_error());
     d_ids.Read(queue_, n * top, ids->data() + lo * top);
     d_terms.Read(queue_, n * top, terms->data() + lo * top);
     d_prob.Read(queue_, n, prob->data() + lo);
@@ -1232,7 +1237,7 @@ void Learner::LinkCommunitySizes(Float min_term, std::vector<uint64_t>* sizes) {
   const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), links.size(), 1,
                                       min_term, nullptr, nullptr, nullptr, d_sizes(), queue_.stream());
   if (rc != AMMSB_OK)
-    throw std::runtime_error(std::string("ammsb_linkcomm_edges: ") + ammsb_strerror(rc) + " (" + ammsb_linkcomm_last_error() + ")");
+    throw PostfitError("ammsb_linkcomm_edges", rc, ammsb_linkcomm_last_error());
   d_sizes.Read(queue_, K + 1, sizes->data());
   queue_.Finish();
 }
@@ -1283,7 +1288,7 @@ void Learner::CommunityQuality(Float threshold, std::vector<uint64_t>* size, std
     rc = ammsb_quality_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), links.size(), d_counts(), nullptr,
                              queue_.stream());
   if (rc != AMMSB_OK)
-    throw std::runtime_error(std::string("ammsb_quality: ") + ammsb_strerror(rc) + " (" + ammsb_quality_last_error() + ")");
+    throw PostfitError("ammsb_quality", rc, ammsb_quality_last_error());
   d_counts.Read(queue_, 2 * K + 2, counts.data());
   queue_.Finish();
   std::copy(counts.begin(), counts.begin() + K, internal->begin());
