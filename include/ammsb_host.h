@@ -29,10 +29,20 @@ int ammsb_host_set_has(const ammsb_host_set* s, const uint64_t* keys, uint64_t n
 /* synthetic a-MMSB graph; returns the number of unique edges written to *edges (malloc'd; free with
  * ammsb_host_free) */
 int64_t ammsb_host_generate_graph(uint64_t N, uint32_t K_true, double avg_degree, uint64_t seed, uint64_t** edges);
+/* the cover that generator plants for the same (N, K_true, seed) as a CSR: *offsets [K_true + 1], *members [the
+ * returned count] node ids, ascending inside a community (both malloc'd; free with ammsb_host_free).  K_true >= 3. */
+int64_t ammsb_host_generate_cover(uint64_t N, uint32_t K_true, uint64_t seed, uint64_t** offsets, uint32_t** members);
 void ammsb_host_free(void* p);
 
 /* SNAP text loader / gzip data-set files (data.cc:36-78, main.cc:109-143) */
 int64_t ammsb_host_load_snap(const char* path, uint64_t* N, uint64_t** edges);
+/* ... and *ids [N]: the file's own id of every dense id (malloc'd; the same edges and the same draws from rand()) */
+int64_t ammsb_host_load_snap_ids(const char* path, uint64_t* N, uint64_t** edges, uint32_t** ids);
+/* A SNAP cmty file (one community per line, `#` lines and blank lines ignored), members sorted and de-duplicated:
+ * *offsets [returned count + 1], *members (both malloc'd).  With ids [n_ids] (load_snap_ids' table) the file's ids
+ * are mapped to dense ids, and those the table does not hold are dropped and counted in *dropped.  -1: unreadable or
+ * malformed. */
+int64_t ammsb_host_read_cover(const char* path, const uint32_t* ids, uint64_t n_ids, uint64_t** offsets, uint32_t** members, uint64_t* dropped);
 int ammsb_host_dump_dataset(const char* path, uint64_t N, float heldout_ratio, const uint64_t* edges, uint64_t n);
 int64_t ammsb_host_load_dataset(const char* path, uint64_t* N, float* heldout_ratio, uint64_t** edges);
 

@@ -94,6 +94,33 @@ class Learner {
   // derived measures as include/ammsb_quality.h defines them (-1 where undefined); floats printed with %.9g.
   bool WriteCommunityQuality(std::ostream* out, Float threshold);
 
+  // Matching the detected cover to a ground-truth cover (include/ammsb_cover.h; not in the reference API).  The detected
+  // community k is {a : pi[a, k] >= threshold} (a binary32 compare); the ground truth is a CSR, offsets [G + 1] ascending
+  // from 0 to members.size(), taken as written (a duplicate counts twice; a member >= N reads nothing and is counted
+  // in `skipped`).  Per ground-truth community the detected community of the best F1 = 2 overlap / (t_g + d_k) among
+  // those it overlaps (equal -> the lower k, none -> -1), the overlap and t_g; the same per detected community over the
+  // ground-truth ones; detected_size = the members of every detected community among all N nodes.  Exact integers.
+  // `overlap`, if not null, receives the dense [G, K] matrix.  Waits for the work in flight as Serialize does, reads
+  // this rank's pi (not a collective), and touches nothing of the iteration.  Throws std::invalid_argument on a
+  // threshold that is negative, NaN or infinite and on offsets that do not describe `members`.
+  struct CoverMatch {
+    std::vector<int32_t> truth_best, detected_best;
+    std::vector<uint32_t> truth_overlap, truth_size, detected_overlap;
+    std::vector<uint64_t> detected_size;
+    uint64_t skipped = 0;
+    // float64, as include/ammsb_cover.h states the measures: the F1 of every best match (0 for none) and the means
+    // over the non-empty communities (-1 where a mean is over nothing); filled by Derive()
+    std::vector<double> f1_truth_each, f1_detected_each;
+    double f1_truth = -1, f1_detected = -1, avg_f1 = -1;
+    void Derive();
+  };
+  void CompareCover(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                    CoverMatch* match, std::vector<uint32_t>* overlap = nullptr);
+  // `# N K G threshold skipped f1_truth f1_detected avg_f1`, then the G lines `t g size best overlap f1` and the K
+  // lines `d k size best overlap f1`; floats printed with %.9g.
+  bool WriteCoverMatch(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
+                       Float threshold);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

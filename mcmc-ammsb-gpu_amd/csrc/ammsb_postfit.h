@@ -1,4 +1,4 @@
-// What the libraries that read a fitted model share (libammsb_readout / _linkpred / _linkcomm / _quality .so): the
+// What the libraries that read a fitted model share (libammsb_readout / _linkpred / _linkcomm / _quality / _cover .so): the
 // descriptor check that decides whether a kernel may issue 16-byte loads, the per-thread error and launch state, the
 // wave-wide selection the exactness claims of DESIGN 4.8 and 4.10 rest on, the block-private counters and the row
 // addressing.

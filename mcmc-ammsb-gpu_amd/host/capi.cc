@@ -64,6 +64,29 @@ int64_t ammsb_host_generate_graph(uint64_t N, uint32_t K_true, double avg_degree
   return *edges ? static_cast<int64_t>(e.size()) : -1;
 }
 
+int64_t ammsb_host_generate_cover(uint64_t N, uint32_t K_true, uint64_t seed, uint64_t** offsets, uint32_t** members) {
+  if (!offsets || !members || N < 2 || K_true < 3) return -1;
+  const std::vector<std::vector<mcmc::Vertex>> c = mcmc::GenerateSyntheticCover(N, K_true, seed);
+  uint64_t total = 0;
+  for (const auto& m : c) total += m.size();
+  uint64_t* off = static_cast<uint64_t*>(malloc(sizeof(uint64_t) * (K_true + 1ull)));
+  uint32_t* mem = static_cast<uint32_t*>(malloc(sizeof(uint32_t) * (total ? total : 1)));
+  if (!off || !mem) {
+    free(off);
+    free(mem);
+    return -1;
+  }
+  uint64_t at = 0;
+  for (uint32_t k = 0; k < K_true; ++k) {
+    off[k] = at;
+    for (const mcmc::Vertex v : c[k]) mem[at++] = static_cast<uint32_t>(v);
+  }
+  off[K_true] = at;
+  *offsets = off;
+  *members = mem;
+  return static_cast<int64_t>(total);
+}
+
 void ammsb_host_free(void* p) { free(p); }
 
 int64_t ammsb_host_load_snap(const char* path, uint64_t* N, uint64_t** edges) {
@@ -71,6 +94,44 @@ int64_t ammsb_host_load_snap(const char* path, uint64_t* N, uint64_t** edges) {
   if (!path || !N || !edges || !mcmc::GetUniqueEdgesFromFile(path, N, &e)) return -1;
   *edges = CopyOut(e);
   return *edges ? static_cast<int64_t>(e.size()) : -1;
+}
+
+int64_t ammsb_host_load_snap_ids(const char* path, uint64_t* N, uint64_t** edges, uint32_t** ids) {
+  std::vector<mcmc::Edge> e;
+  std::vector<mcmc::Vertex> original;
+  if (!path || !N || !edges || !ids || !mcmc::GetUniqueEdgesFromFile(path, N, &e, &original)) return -1;
+  uint32_t* out = static_cast<uint32_t*>(malloc(sizeof(uint32_t) * (original.size() ? original.size() : 1)));
+  if (!out) return -1;
+  std::copy(original.begin(), original.end(), out);
+  *edges = CopyOut(e);
+  if (!*edges) {
+    free(out);
+    return -1;
+  }
+  *ids = out;
+  return static_cast<int64_t>(e.size());
+}
+
+int64_t ammsb_host_read_cover(const char* path, const uint32_t* ids, uint64_t n_ids, uint64_t** offsets,
+                              uint32_t** members, uint64_t* dropped) {
+  if (!path || !offsets || !members || !dropped || (!ids && n_ids)) return -1;
+  std::vector<mcmc::Vertex> original;
+  if (ids) original.assign(ids, ids + n_ids);
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> mem;
+  if (!mcmc::ReadCover(path, ids ? &original : nullptr, &off, &mem, dropped)) return -1;
+  uint64_t* o = static_cast<uint64_t*>(malloc(sizeof(uint64_t) * off.size()));
+  uint32_t* m = static_cast<uint32_t*>(malloc(sizeof(uint32_t) * (mem.size() ? mem.size() : 1)));
+  if (!o || !m) {
+    free(o);
+    free(m);
+    return -1;
+  }
+  std::copy(off.begin(), off.end(), o);
+  std::copy(mem.begin(), mem.end(), m);
+  *offsets = o;
+  *members = m;
+  return static_cast<int64_t>(off.size() - 1);
 }
 
 int ammsb_host_dump_dataset(const char* path, uint64_t N, float heldout_ratio, const uint64_t* edges, uint64_t n) {

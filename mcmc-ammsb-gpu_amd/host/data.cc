@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <thread>
 #include <sched.h>
+#include <cctype>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +51,11 @@ void Graph::ExportCSR(std::vector<uint64_t>* offsets, std::vector<Vertex>* targe
 // -------------------------------------------------------------------------------- text loader
 
 bool GetUniqueEdgesFromFile(const std::string& filename, uint64_t* count_vertices, std::vector<Edge>* vals) {
+  return GetUniqueEdgesFromFile(filename, count_vertices, vals, nullptr);
+}
+
+bool GetUniqueEdgesFromFile(const std::string& filename, uint64_t* count_vertices, std::vector<Edge>* vals,
+                            std::vector<Vertex>* original_ids) {
   std::ifstream in(filename);
   if (!in.is_open()) return false;
   std::string line;
@@ -68,6 +75,10 @@ bool GetUniqueEdgesFromFile(const std::string& filename, uint64_t* count_vertice
   Vertex next = 0;
   for (Vertex v : seen) dense[v] = next++;
   *count_vertices = dense.size();
+  if (original_ids) {
+    original_ids->assign(dense.size(), 0);
+    for (const auto& kv : dense) (*original_ids)[kv.second] = kv.first;
+  }
   for (Edge e : raw) {
     Vertex u, v;
     std::tie(u, v) = Vertices(e);
@@ -79,6 +90,48 @@ bool GetUniqueEdgesFromFile(const std::string& filename, uint64_t* count_vertice
   // over the global rand():
   for (size_t i = 1; i < vals->size(); ++i) std::swap((*vals)[i], (*vals)[rand() % (i + 1)]);
   return true;
+}
+
+// ------------------------------------------------------------------------ ground-truth cover
+
+bool ReadCover(const std::string& filename, const std::vector<Vertex>* original_ids, std::vector<uint64_t>* offsets,
+               std::vector<uint32_t>* members, uint64_t* dropped) {
+  std::ifstream in(filename);
+  if (!in.is_open()) return false;
+  std::unordered_map<Vertex, Vertex> dense;
+  if (original_ids)
+    for (size_t d = 0; d < original_ids->size(); ++d) dense[(*original_ids)[d]] = static_cast<Vertex>(d);
+  offsets->assign(1, 0);
+  members->clear();
+  *dropped = 0;
+  std::string line;
+  while (std::getline(in, line)) {
+    const size_t first = line.find_first_not_of(" \t\r\n\f\v");
+    if (first == std::string::npos || line[first] == '#') continue;
+    const size_t lo = members->size();
+    const char* p = line.c_str() + first;
+    while (*p) {
+      if (*p < '0' || *p > '9') return false;  // (a sign, a letter: not an id)
+      char* end;
+      errno = 0;
+      const unsigned long long id = strtoull(p, &end, 10);
+      if (errno || (*end && !isspace(static_cast<unsigned char>(*end)))) return false;
+      p = end;
+      while (*p && isspace(static_cast<unsigned char>(*p))) ++p;
+      if (original_ids) {
+        const auto it = id <= 0xFFFFFFFFull ? dense.find(static_cast<Vertex>(id)) : dense.end();
+        if (it == dense.end()) ++*dropped;
+        else members->push_back(it->second);
+      } else {
+        if (id > 0xFFFFFFFFull) return false;
+        members->push_back(static_cast<uint32_t>(id));
+      }
+    }
+    std::sort(members->begin() + lo, members->end());
+    members->erase(std::unique(members->begin() + lo, members->end()), members->end());
+    offsets->push_back(members->size());
+  }
+  return !in.bad();
 }
 
 // ------------------------------------------------------------------------ train / held-out
@@ -221,18 +274,21 @@ static void ParallelSort(std::vector<Edge>* v) {
   }
 }
 
-std::vector<Edge> GenerateSyntheticGraph(uint64_t N, uint32_t K_true, double avg_degree, uint64_t seed) {
-  SplitMix64 rng{seed};
-  // memberships: 1-3 communities per node (uniform count, uniform choice)
+namespace {
+
+// memberships: 1-3 communities per node (uniform count, uniform choice), the first thing drawn from the stream, so
+// that the generator and GenerateSyntheticCover plant the same cover.  (A node draws up to three distinct communities:
+// K_true >= 3.)
+std::vector<std::vector<Vertex>> DrawMemberships(SplitMix64* rng, uint64_t N, uint32_t K_true) {
   std::vector<std::vector<Vertex>> members(K_true);
   for (uint64_t v = 0; v < N; ++v) {
-    const unsigned cnt = 1 + static_cast<unsigned>(rng.below(3));
+    const unsigned cnt = 1 + static_cast<unsigned>(rng->below(3));
     unsigned got[3];
     for (unsigned c = 0; c < cnt; ++c) {
       unsigned k;
       bool dup;
       do {
-        k = static_cast<unsigned>(rng.below(K_true));
+        k = static_cast<unsigned>(rng->below(K_true));
         dup = false;
         for (unsigned d = 0; d < c; ++d) dup |= (got[d] == k);
       } while (dup);
@@ -240,6 +296,19 @@ std::vector<Edge> GenerateSyntheticGraph(uint64_t N, uint32_t K_true, double avg
       members[k].push_back(static_cast<Vertex>(v));
     }
   }
+  return members;
+}
+
+}  // namespace
+
+std::vector<std::vector<Vertex>> GenerateSyntheticCover(uint64_t N, uint32_t K_true, uint64_t seed) {
+  SplitMix64 rng{seed};
+  return DrawMemberships(&rng, N, K_true);
+}
+
+std::vector<Edge> GenerateSyntheticGraph(uint64_t N, uint32_t K_true, double avg_degree, uint64_t seed) {
+  SplitMix64 rng{seed};
+  const std::vector<std::vector<Vertex>> members = DrawMemberships(&rng, N, K_true);
   // community strengths beta_k ~ U(0.3, 0.7); the number of intra-community edges is proportional
   // to beta_k * |C_k|^2 and scaled so that the total is N * avg_degree / 2
   std::vector<double> weight(K_true);

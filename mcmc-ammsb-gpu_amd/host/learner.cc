@@ -10,6 +10,7 @@
 #include "ammsb_linkpred.h"
 #include "ammsb_linkcomm.h"
 #include "ammsb_quality.h"
+#include "ammsb_cover.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1313,6 +1314,99 @@ bool Learner::WriteCommunityQuality(std::ostream* out, Float threshold) {
     snprintf(num, sizeof(num), "%.9g", cond);
     snprintf(num2, sizeof(num2), "%.9g", dens);
     *out << k << " " << size[k] << " " << internal[k] << " " << boundary[k] << " " << num << " " << num2 << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- matching the detected cover to a ground-truth cover: libammsb_cover.so over pi and the member list
+void Learner::CoverMatch::Derive() {
+  // one formula with _cover.py: F1 = 2 o / (t + d) in float64, the means added in index order
+  const auto each = [](const std::vector<int32_t>& best, const std::vector<uint32_t>& over, auto own, auto other,
+                       std::vector<double>* f1, double* mean) {
+    f1->assign(best.size(), 0.0);
+    double sum = 0;
+    uint64_t present = 0;
+    for (size_t i = 0; i < best.size(); ++i) {
+      if (best[i] >= 0 && over[i] > 0)
+        (*f1)[i] = 2.0 * static_cast<double>(over[i]) / (static_cast<double>(own(i)) + static_cast<double>(other(best[i])));
+      if (own(i) > 0) {
+        sum += (*f1)[i];
+        ++present;
+      }
+    }
+    *mean = present ? sum / static_cast<double>(present) : -1.0;
+  };
+  const auto t = [this](size_t g) { return static_cast<uint64_t>(truth_size[g]); };
+  const auto d = [this](size_t k) { return detected_size[k]; };
+  each(truth_best, truth_overlap, t, d, &f1_truth_each, &f1_truth);
+  each(detected_best, detected_overlap, d, t, &f1_detected_each, &f1_detected);
+  avg_f1 = f1_truth >= 0 && f1_detected >= 0 ? (f1_truth + f1_detected) / 2.0 : -1.0;
+}
+
+void Learner::CompareCover(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                           CoverMatch* m, std::vector<uint32_t>* overlap) {
+  if (!(threshold >= 0 && std::isfinite(threshold)))
+    throw std::invalid_argument("CompareCover: the threshold must be finite and >= 0");
+  if (offsets.empty() || offsets.front() != 0 || offsets.back() != members.size() ||
+      !std::is_sorted(offsets.begin(), offsets.end()))
+    throw std::invalid_argument("CompareCover: offsets must ascend from 0 to the number of members");
+  const uint64_t G = offsets.size() - 1, M = members.size(), K = pi_->Cols();
+  if ((G >> 31) || (M >> 32)) throw std::invalid_argument("CompareCover: 2^31 communities or 2^32 members, or more");
+  Memberships(1, threshold, nullptr, nullptr, nullptr, &m->detected_size);  // (drains; sizes only)
+  m->truth_best.assign(G, -1);
+  m->truth_overlap.assign(G, 0);
+  m->truth_size.assign(G, 0);
+  m->detected_best.assign(K, -1);
+  m->detected_overlap.assign(K, 0);
+  m->skipped = 0;
+  if (overlap) overlap->assign(G * K, 0);
+  if (G > 0 && M > 0) {  // (with nothing to compare the library launches nothing: every community is unmatched)
+    const uint64_t ws_bytes = ammsb_cover_workspace_bytes(M, static_cast<uint32_t>(K));
+    if (ws_bytes == 0) throw std::runtime_error("CompareCover: K outside 1..8192");
+    const clcuda::Context context = queue_.GetContext();
+    clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
+    clcuda::Buffer<uint32_t> d_members(context, queue_, members.begin(), members.end());
+    clcuda::Buffer<uint64_t> d_dsize(context, queue_, m->detected_size.begin(), m->detected_size.end());
+    clcuda::Buffer<int32_t> d_tbest(context, G), d_dbest(context, K);
+    clcuda::Buffer<uint32_t> d_tover(context, G), d_tsize(context, G), d_dover(context, K);
+    clcuda::Buffer<uint32_t> d_dense(context, overlap ? G * K : 1);
+    clcuda::Buffer<uint64_t> d_skipped(context, 1), d_ws(context, (ws_bytes + 7) / 8);
+    const int rc = ammsb_cover_match(&pi_->Get(), threshold, d_offsets(), G, d_members(), M, d_dsize(), d_tbest(),
+                                     d_tover(), d_tsize(), d_dbest(), d_dover(), d_skipped(),
+                                     overlap ? d_dense() : nullptr, d_ws(), ws_bytes, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw PostfitError("ammsb_cover_match", rc, ammsb_cover_last_error());
+    d_tbest.Read(queue_, G, m->truth_best.data());
+    d_tover.Read(queue_, G, m->truth_overlap.data());
+    d_tsize.Read(queue_, G, m->truth_size.data());
+    d_dbest.Read(queue_, K, m->detected_best.data());
+    d_dover.Read(queue_, K, m->detected_overlap.data());
+    d_skipped.Read(queue_, 1, &m->skipped);
+    if (overlap) d_dense.Read(queue_, G * K, overlap->data());
+    queue_.Finish();
+  }
+  m->Derive();
+}
+
+bool Learner::WriteCoverMatch(std::ostream* out, const std::vector<uint64_t>& offsets,
+                              const std::vector<uint32_t>& members, Float threshold) {
+  CoverMatch m;
+  CompareCover(offsets, members, threshold, &m);
+  char a[32], b[32], c[32], d[32];
+  snprintf(a, sizeof(a), "%.9g", static_cast<double>(threshold));
+  snprintf(b, sizeof(b), "%.9g", m.f1_truth);
+  snprintf(c, sizeof(c), "%.9g", m.f1_detected);
+  snprintf(d, sizeof(d), "%.9g", m.avg_f1);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << m.truth_best.size() << " " << a << " " << m.skipped << " "
+       << b << " " << c << " " << d << "\n";
+  for (size_t g = 0; g < m.truth_best.size(); ++g) {
+    snprintf(a, sizeof(a), "%.9g", m.f1_truth_each[g]);
+    *out << "t " << g << " " << m.truth_size[g] << " " << m.truth_best[g] << " " << m.truth_overlap[g] << " " << a << "\n";
+  }
+  for (size_t k = 0; k < m.detected_best.size(); ++k) {
+    snprintf(a, sizeof(a), "%.9g", m.f1_detected_each[k]);
+    *out << "d " << k << " " << m.detected_size[k] << " " << m.detected_best[k] << " " << m.detected_overlap[k] << " " << a
+         << "\n";
   }
   return static_cast<bool>(*out);
 }

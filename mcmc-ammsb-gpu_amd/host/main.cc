@@ -77,7 +77,9 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut;
+  bool haveCoverThreshold = false;
+  double coverThreshold = 0.05;
   bool haveQualityThreshold = false;
   double qualityThreshold = 0.05;
   bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
@@ -178,6 +180,15 @@ int main(int argc, char** argv) {
                in >> qualityThreshold;
                return !in.fail() && in.eof();
              }},
+      OptStr("ground-truth", 0, &groundTruth),  // (new, with --cover-match-out) a SNAP cmty file: one community per line; the graph file's own ids with --file, dense ids with --load-data
+      OptStr("cover-match-out", 0, &coverMatchOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold skipped f1_truth f1_detected avg_f1`, then `t g size best overlap f1` per ground-truth and `d k size best overlap f1` per detected community
+      Option{"cover-match-threshold", 0, "0.05 (new, with --ground-truth and --cover-match-out: a node is a member of k iff pi[a, k] >= it)",
+             [&](const std::string& v) {
+               haveCoverThreshold = true;
+               std::istringstream in(v);
+               in >> coverThreshold;
+               return !in.fail() && in.eof();
+             }},
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -259,6 +270,10 @@ int main(int argc, char** argv) {
   if (haveQualityThreshold && qualityOut.empty()) Fatal("--community-quality-threshold needs --community-quality-out FILE");
   if (!(qualityThreshold >= 0) || !std::isfinite(static_cast<float>(qualityThreshold)))
     Fatal("--community-quality-threshold must be finite and >= 0");
+  if (groundTruth.empty() != coverMatchOut.empty()) Fatal("--ground-truth FILE and --cover-match-out FILE need each other");
+  if (haveCoverThreshold && coverMatchOut.empty()) Fatal("--cover-match-threshold needs --ground-truth FILE and --cover-match-out FILE");
+  if (!(coverThreshold >= 0) || !std::isfinite(static_cast<float>(coverThreshold)))
+    Fatal("--cover-match-threshold must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -282,8 +297,9 @@ int main(int argc, char** argv) {
   if (dumpDataset && dumpFile.empty()) Fatal("dump-file is required with dump-data");
 
   std::vector<mcmc::Edge> unique_edges;
+  std::vector<mcmc::Vertex> originalIds;  // of a text graph: the file's id of every dense id
   if (!loadDataset) {
-    if (!mcmc::GetUniqueEdgesFromFile(filename, &cfg.N, &unique_edges)) Fatal("Failed to generate sets from file " + filename);
+    if (!mcmc::GetUniqueEdgesFromFile(filename, &cfg.N, &unique_edges, &originalIds)) Fatal("Failed to generate sets from file " + filename);
     if (dumpDataset) {  // main.cc:110-127: dump and stop
       if (!mcmc::DumpDataset(dumpFile, cfg.N, cfg.heldout_ratio, unique_edges)) Fatal("cannot write " + dumpFile);
       return 0;
@@ -294,6 +310,16 @@ int main(int argc, char** argv) {
   if (!mcmc::GenerateSetsFromEdges(cfg.N, unique_edges, cfg.heldout_ratio, &cfg.training_edges, &cfg.heldout_edges,
                                    &cfg.training, &cfg.heldout))
     Fatal("Failed to generate training/heldout sets");
+  std::vector<uint64_t> truthOffsets;
+  std::vector<uint32_t> truthMembers;
+  if (!groundTruth.empty()) {
+    // a text graph's ground truth speaks of the graph file's own ids, a data-set dump's of dense ids
+    uint64_t dropped = 0;
+    if (!mcmc::ReadCover(groundTruth, loadDataset ? nullptr : &originalIds, &truthOffsets, &truthMembers, &dropped))
+      Fatal("cannot read --ground-truth file " + groundTruth);
+    std::cerr << "I ground truth " << groundTruth << ": " << truthOffsets.size() - 1 << " communities, "
+              << truthMembers.size() << " members, " << dropped << " ids the graph never mentions dropped" << std::endl;
+  }
   for (mcmc::Vertex v : linkNodes)
     if (v >= cfg.N) Fatal("--links-nodes: node id " + std::to_string(v) + " >= N = " + std::to_string(cfg.N));
   cfg.trainingGraph.reset(new mcmc::Graph(cfg.N, cfg.training_edges));
@@ -406,6 +432,18 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("community quality: ") + e.what());
+    }
+  }
+  if (!coverMatchOut.empty()) {
+    // every rank holds all of pi: the comparison is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(coverMatchOut);
+        if (!out.good() || !learner.WriteCoverMatch(&out, truthOffsets, truthMembers, static_cast<mcmc::Float>(coverThreshold)))
+          Fatal("cannot write cover match " + coverMatchOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("cover match: ") + e.what());
     }
   }
   learner.PrintStats();

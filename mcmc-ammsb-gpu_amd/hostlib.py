@@ -26,8 +26,14 @@ SIGNATURES = {
     "ammsb_host_set_data": (C.POINTER(C.c_uint64), [_vp]),
     "ammsb_host_set_has": (C.c_int, [_vp, _u64p, _u64, _u8p]),
     "ammsb_host_generate_graph": (C.c_int64, [_u64, _u32, C.c_double, _u64, C.POINTER(C.POINTER(C.c_uint64))]),
+    "ammsb_host_generate_cover": (C.c_int64, [_u64, _u32, _u64, C.POINTER(C.POINTER(C.c_uint64)),
+                                              C.POINTER(C.POINTER(C.c_uint32))]),
     "ammsb_host_free": (None, [_vp]),
     "ammsb_host_load_snap": (C.c_int64, [C.c_char_p, C.POINTER(_u64), C.POINTER(C.POINTER(C.c_uint64))]),
+    "ammsb_host_load_snap_ids": (C.c_int64, [C.c_char_p, C.POINTER(_u64), C.POINTER(C.POINTER(C.c_uint64)),
+                                             C.POINTER(C.POINTER(C.c_uint32))]),
+    "ammsb_host_read_cover": (C.c_int64, [C.c_char_p, _vp, _u64, C.POINTER(C.POINTER(C.c_uint64)),
+                                          C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(_u64)]),
     "ammsb_host_dump_dataset": (C.c_int, [C.c_char_p, _u64, C.c_float, _u64p, _u64]),
     "ammsb_host_load_dataset": (C.c_int64, [C.c_char_p, C.POINTER(_u64), C.POINTER(C.c_float),
                                             C.POINTER(C.POINTER(C.c_uint64))]),
@@ -66,7 +72,7 @@ def load():
 
 
 def _take(ptr, n):
-    """Copy a malloc'd u64 array into numpy and free it."""
+    """Copy a malloc'd array into numpy and free it."""
     out = np.ctypeslib.as_array(ptr, shape=(max(int(n), 1),))[:int(n)].copy()
     load().ammsb_host_free(C.cast(ptr, C.c_void_p))
     return out
@@ -124,12 +130,51 @@ def generate_graph(N, K_true, avg_degree, seed=20260101):
     return _take(p, n)
 
 
+def generate_cover(N, K_true, seed=20260101):
+    """The cover generate_graph plants for the same (N, K_true, seed) (mcmc::GenerateSyntheticCover): 1-3 communities
+    per node.  -> (offsets [K_true + 1] uint64, members uint32), node ids ascending inside a community."""
+    po, pm = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)()
+    n = load().ammsb_host_generate_cover(N, K_true, seed, C.byref(po), C.byref(pm))
+    if n < 0:
+        raise AmmsbError("cover generation failed (it needs N >= 2 and K_true >= 3)")
+    try:
+        offsets = np.ctypeslib.as_array(po, shape=(K_true + 1,)).copy()
+        members = np.ctypeslib.as_array(pm, shape=(max(n, 1),))[:n].copy()
+    finally:
+        load().ammsb_host_free(C.cast(po, C.c_void_p))
+        load().ammsb_host_free(C.cast(pm, C.c_void_p))
+    return offsets, members
+
+
 def load_snap(path):
     p, N = C.POINTER(C.c_uint64)(), _u64()
     n = load().ammsb_host_load_snap(path.encode(), C.byref(N), C.byref(p))
     if n < 0:
         raise AmmsbError("cannot read %s" % path)
     return int(N.value), _take(p, n)
+
+
+def load_snap_ids(path):
+    """-> (N, edges, ids): load_snap, and ids [N] uint32 = the file's own id of every dense id"""
+    p, q, N = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), _u64()
+    n = load().ammsb_host_load_snap_ids(path.encode(), C.byref(N), C.byref(p), C.byref(q))
+    if n < 0:
+        raise AmmsbError("cannot read %s" % path)
+    return int(N.value), _take(p, n), _take(q, N.value)
+
+
+def read_cover(path, ids=None):
+    """mcmc::ReadCover, the C++ reader of a SNAP cmty file (_cover.read_cover is its Python twin): ids = load_snap_ids'
+    table or None for dense ids.  -> (offsets [G + 1] uint64, members [M] uint32, dropped)"""
+    po, pm, dropped = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), _u64()
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    G = load().ammsb_host_read_cover(path.encode(), None if ids is None else ids.ctypes.data, 0 if ids is None else ids.size,
+                                     C.byref(po), C.byref(pm), C.byref(dropped))
+    if G < 0:
+        raise AmmsbError("cannot read the cover %s" % path)
+    offsets = _take(po, G + 1)
+    return offsets, _take(pm, offsets[-1]), int(dropped.value)
 
 
 def dump_dataset(path, N, heldout_ratio, edges):

@@ -1240,6 +1240,35 @@ class Learner:
         _, shared = cq.edges(cq.mask(self.pi, threshold), self.cfg.N, self.cfg.K, edges, shared=True, counts=False)
         return shared
 
+    # ---- comparing with a ground-truth cover (include/ammsb_cover.h).  Like the other read-outs: drained first, local
+    # on any rank, no CPU path, and nothing of the iteration is touched.
+    def _cover(self):
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the cover match has no CPU path")
+        if getattr(self, "_cover_match", None) is None:
+            self._cover_match = self.ops.CoverMatch(self.ctx)
+        return self._cover_match
+
+    def CompareCover(self, truth, threshold=0.05, dense=False):
+        """-> _cover.Match: the detected cover D_k = {a : pi[a, k] >= threshold} against the ground-truth cover `truth`,
+        (offsets [G + 1], members [M]) host arrays or a list of id lists (taken as written: a duplicate counts twice; a
+        member >= N reads nothing and is counted in .skipped).  Per ground-truth community the detected community of the
+        best F1 = 2 overlap / (t_g + d_k) among those it overlaps (equal F1 -> the lower k, none -> -1), with the overlap
+        and t_g; the same per detected community over the ground-truth ones; d_k = CommunitySizes(threshold) counts all
+        N nodes, also those no ground-truth community holds.  In float64 on the host: the F1 of every best match and
+        f1_truth, f1_detected, avg_f1 (-1 where a mean is over nothing).  dense=True also returns overlap [G, K].  The
+        integers are exact."""
+        from . import _cover
+        threshold = _cover.check_threshold(threshold)
+        offsets, members = _cover.check_cover(truth)
+        cm = self._cover()
+        self.drain()
+        size = self._readout().sizes(self.pi, threshold)
+        tb, to, ts, db, do, sk, ov = cm.match(self.pi, threshold, offsets, members, size, dense)
+        u32 = lambda x: x.cpu().numpy().view(np.uint32)   # noqa: E731
+        return _cover.Match(threshold, tb.cpu().numpy(), u32(to), u32(ts), db.cpu().numpy(), u32(do),
+                            size.cpu().numpy(), int(sk.item()), None if ov is None else u32(ov))
+
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
         out("SAMPLING : %.6f (%%%.2f)" % (self.samplingTime, 100 * self.samplingTime / max(self.time, 1e-12)))

@@ -1044,6 +1044,66 @@ class CommunityQuality:
         return self.q.last_kernel_name()
 
 
+class CoverMatch:
+    """Matching the detected cover to a ground-truth cover (include/ammsb_cover.h): per ground-truth community the
+    detected community of the best F1 and per detected community the ground-truth one, from one gather pass over the
+    rows of pi that the members name.  Integer counts over binary32 compares and integer compares of rationals: exact.
+    Owns its workspace, which only ever grows: reserve() it outside a timed path."""
+
+    def __init__(self, ctx):
+        from . import _cover
+        self.ctx = ctx
+        self.cv = _cover
+        self.lib = _cover.load()
+        self.workspace = None
+
+    def workspace_bytes(self, M, K):
+        return int(self.lib.ammsb_cover_workspace_bytes(int(M), int(K)))
+
+    def reserve(self, nbytes):
+        """Grow the workspace to nbytes (torch's allocator: not for a timed path)."""
+        if self.workspace is None or self.workspace.numel() * 8 < nbytes:
+            self.workspace = self.ctx.empty(((int(nbytes) + 7) // 8,), torch.int64)
+        return self.workspace
+
+    def match(self, pi, threshold, offsets, members, detected_size, dense=False):
+        """offsets [G + 1] (uint64 bits) and members [M] (uint32 bits): host arrays or contiguous int64 / int32 device
+        tensors; detected_size: the [K] int64 device tensor CommunityReadout.sizes gives at the same threshold.
+        -> (truth_best [G] int32, truth_overlap [G] int32, truth_size [G] int32, detected_best [K] int32,
+        detected_overlap [K] int32, skipped [1] int64, overlap [G, K] int32 or None) on the device; the uint32 outputs
+        come back as int32 bits.  With nothing to compare (G == 0 or M == 0) every community is unmatched."""
+        thr = self.cv.check_threshold(threshold)
+        if not torch.is_tensor(offsets):
+            offsets = self.ctx.from_numpy(np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1))
+        if not torch.is_tensor(members):
+            members = self.ctx.from_numpy(np.ascontiguousarray(members, dtype=np.uint32).reshape(-1))
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
+            raise AmmsbError("cover match: offsets must be a contiguous 1-d int64 (uint64 bits) device tensor [G + 1]")
+        if members.dtype != torch.int32 or members.dim() != 1 or not members.is_contiguous():
+            raise AmmsbError("cover match: members must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        if detected_size.dtype != torch.int64 or detected_size.numel() != pi.cols or not detected_size.is_contiguous():
+            raise AmmsbError("cover match: detected_size must be a contiguous [K] int64 device tensor")
+        G, M, K = int(offsets.numel()) - 1, int(members.numel()), int(pi.cols)
+        c = self.ctx
+        tb, to, ts = c.empty((G,), torch.int32).fill_(-1), c.zeros((G,), torch.int32), c.zeros((G,), torch.int32)
+        db, do = c.empty((K,), torch.int32).fill_(-1), c.zeros((K,), torch.int32)
+        sk = c.zeros((1,), torch.int64)
+        ov = c.zeros((G, K), torch.int32) if dense else None
+        if G and M:  # (with nothing to compare the library launches nothing: the presets stand)
+            nbytes = self.workspace_bytes(M, K)
+            if nbytes == 0:
+                raise AmmsbError("cover match: no workspace for %d members against %d communities" % (M, K))
+            ws = self.reserve(nbytes)
+            self.cv.check(self.lib.ammsb_cover_match(C.byref(pi.desc), thr, _ptr(offsets), G, _ptr(members), M,
+                                                     _ptr(detected_size), _ptr(tb), _ptr(to), _ptr(ts), _ptr(db),
+                                                     _ptr(do), _ptr(sk), _ptr(ov), _ptr(ws), ws.numel() * 8,
+                                                     _stream()))
+        return tb, to, ts, db, do, sk, ov
+
+    def kernel_name(self):
+        return self.cv.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

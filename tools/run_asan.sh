@@ -19,4 +19,4 @@ python -m pytest -x -q -m "not gpu" tests/test_host_lib.py tests/test_oracle_sam
 unset LD_PRELOAD AMMSB_HOST_LIB AMMSB_ORACLE_LIB
 export AMMSB_MAIN_EXE=$PWD/mcmc-ammsb-gpu_amd/ammsb_main_asan
 export AMMSB_XT_EXE=$PWD/mcmc-ammsb-gpu_amd/exchange_test_asan
-python -m pytest -x -q -m "not gpu" tests/test_cli.py tests/test_cpp_exchange.py tests/test_readout_host.py tests/test_linkpred_host.py tests/test_linkcomm_host.py tests/test_quality_host.py -p no:cacheprovider "$@"
+python -m pytest -x -q -m "not gpu" tests/test_cli.py tests/test_cpp_exchange.py tests/test_readout_host.py tests/test_linkpred_host.py tests/test_linkcomm_host.py tests/test_quality_host.py tests/test_cover_host.py -p no:cacheprovider "$@"
