@@ -121,6 +121,27 @@ class Learner {
   bool WriteCoverMatch(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
                        Float threshold);
 
+  // The overlapping NMI of the detected cover against the same kind of ground truth (include/ammsb_nmi.h): the dense
+  // overlap is made slab by slab (Gs communities with Gs K 4 <= slab_bytes, Gs >= 1) by the cover match and folded on
+  // the device into one minimum per community; every float comes from the device, the host applies the fallback
+  // h = min(c, H) and adds in index order.  NMI is defined on sets: std::invalid_argument on a community that lists a
+  // node twice, besides what CompareCover throws.  Waits, reads and perturbs like CompareCover.
+  struct CoverNmi {
+    std::vector<uint32_t> truth_size;
+    std::vector<uint64_t> detected_size;
+    uint64_t skipped = 0;
+    std::vector<double> H_truth, H_detected;  // H(X_g), H(Y_k)
+    std::vector<double> h_truth, h_detected;  // H(X_g | Y), H(Y_k | X)
+    double nmi_lfk = -1, nmi_max = -1;        // -1 where undefined
+    void Derive();                            // the two scores from the four arrays
+  };
+  void CoverNMI(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                CoverNmi* nmi, uint64_t slab_bytes = 256ull << 20);
+  // `# N K G threshold skipped nmi_lfk nmi_max`, then the G lines `t g size H h` and the K lines `d k size H h`;
+  // floats printed with %.17g.
+  bool WriteCoverNMI(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
+                     Float threshold, uint64_t slab_bytes = 256ull << 20);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

@@ -11,6 +11,7 @@
 #include "ammsb_linkcomm.h"
 #include "ammsb_quality.h"
 #include "ammsb_cover.h"
+#include "ammsb_nmi.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1407,6 +1408,139 @@ bool Learner::WriteCoverMatch(std::ostream* out, const std::vector<uint64_t>& of
     snprintf(a, sizeof(a), "%.9g", m.f1_detected_each[k]);
     *out << "d " << k << " " << m.detected_size[k] << " " << m.detected_best[k] << " " << m.detected_overlap[k] << " " << a
          << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- the overlapping NMI against a ground-truth cover: libammsb_cover.so for the dense overlap of a slab,
+// libammsb_nmi.so for the pair pass
+void Learner::CoverNmi::Derive() {
+  // one formula with _nmi.py (include/ammsb_nmi.h), the sums added in index order
+  const auto side = [](const std::vector<double>& H, const std::vector<double>& h, double* mean, double* sumH,
+                       double* sumh) {
+    double ratios = 0;
+    uint64_t present = 0;
+    *sumH = *sumh = 0;
+    for (size_t i = 0; i < H.size(); ++i) {
+      if (H[i] > 0) {
+        ratios += h[i] / H[i];
+        ++present;
+      }
+      *sumH += H[i];
+      *sumh += h[i];
+    }
+    *mean = present ? ratios / static_cast<double>(present) : -1.0;
+  };
+  double mx, my, HX, hX, HY, hY;
+  side(H_truth, h_truth, &mx, &HX, &hX);
+  side(H_detected, h_detected, &my, &HY, &hY);
+  nmi_lfk = mx < 0 || my < 0 ? -1.0 : 1.0 - 0.5 * (mx + my);
+  const double den = std::max(HX, HY);
+  nmi_max = den > 0 ? 0.5 * (HX - hX + HY - hY) / den : -1.0;
+}
+
+void Learner::CoverNMI(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                       CoverNmi* r, uint64_t slab_bytes) {
+  if (!(threshold >= 0 && std::isfinite(threshold)))
+    throw std::invalid_argument("CoverNMI: the threshold must be finite and >= 0");
+  if (offsets.empty() || offsets.front() != 0 || offsets.back() != members.size() ||
+      !std::is_sorted(offsets.begin(), offsets.end()))
+    throw std::invalid_argument("CoverNMI: offsets must ascend from 0 to the number of members");
+  const uint64_t G = offsets.size() - 1, M = members.size(), K = pi_->Cols(), N = pi_->Rows();
+  if ((G >> 31) || (M >> 32)) throw std::invalid_argument("CoverNMI: 2^31 communities or 2^32 members, or more");
+  {  // NMI is defined on sets
+    std::vector<uint32_t> sorted;
+    for (uint64_t g = 0; g < G; ++g) {
+      sorted.assign(members.begin() + offsets[g], members.begin() + offsets[g + 1]);
+      std::sort(sorted.begin(), sorted.end());
+      if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        throw std::invalid_argument("CoverNMI: ground-truth community " + std::to_string(g) +
+                                    " lists a node twice (NMI is defined on sets)");
+    }
+  }
+  Memberships(1, threshold, nullptr, nullptr, nullptr, &r->detected_size);  // (drains; sizes only)
+  r->truth_size.assign(G, 0);
+  r->skipped = 0;
+  for (uint64_t g = 0; g < G; ++g)
+    for (uint64_t i = offsets[g]; i < offsets[g + 1]; ++i) {
+      if (members[i] < N) ++r->truth_size[g];
+      else ++r->skipped;
+    }
+  r->H_truth.assign(G, 0);
+  r->h_truth.assign(G, 0);
+  r->H_detected.assign(K, 0);
+  r->h_detected.assign(K, 0);
+  if (K == 0 || K > AMMSB_NMI_MAX_COLS) throw std::runtime_error("CoverNMI: K outside 1..8192");
+  const clcuda::Context context = queue_.GetContext();
+  const uint64_t rows = std::min<uint64_t>(std::max<uint64_t>(G, 1), std::max<uint64_t>(1, slab_bytes / (4 * K)));
+  uint64_t most_members = 1;  // of a slab
+  for (uint64_t g0 = 0; g0 < G; g0 += rows)
+    most_members = std::max(most_members, offsets[std::min(g0 + rows, G)] - offsets[g0]);
+  const uint64_t ws_bytes = std::max<uint64_t>(8, ammsb_cover_workspace_bytes(most_members, static_cast<uint32_t>(K)));
+  clcuda::Buffer<uint32_t> d_tsize(context, std::max<uint64_t>(G, 1));
+  if (G) d_tsize.Write(queue_, G, r->truth_size.data());
+  clcuda::Buffer<uint64_t> d_dsize(context, queue_, r->detected_size.begin(), r->detected_size.end());
+  clcuda::Buffer<double> d_HX(context, std::max<uint64_t>(G, 1)), d_cX(context, std::max<uint64_t>(G, 1));
+  clcuda::Buffer<double> d_HY(context, K), d_cY(context, K);
+  int rc = ammsb_nmi_begin(N, d_tsize(), G, d_dsize(), static_cast<uint32_t>(K), d_HX(), d_HY(), d_cX(), d_cY(),
+                           queue_.stream());
+  if (rc != AMMSB_OK) throw PostfitError("ammsb_nmi_begin", rc, ammsb_nmi_last_error());
+  if (G > 0) {
+    clcuda::Buffer<uint64_t> d_offsets(context, rows + 1), d_skipped(context, 1), d_ws(context, (ws_bytes + 7) / 8);
+    clcuda::Buffer<uint32_t> d_members(context, most_members), d_dense(context, rows * K);
+    clcuda::Buffer<int32_t> d_tbest(context, rows), d_dbest(context, K);
+    clcuda::Buffer<uint32_t> d_tover(context, rows), d_ts(context, rows), d_dover(context, K);
+    std::vector<uint64_t> rebased;
+    for (uint64_t g0 = 0; g0 < G; g0 += rows) {
+      const uint64_t g1 = std::min(g0 + rows, G), Gs = g1 - g0, Ms = offsets[g1] - offsets[g0];
+      if (Ms > 0) {
+        rebased.assign(offsets.begin() + g0, offsets.begin() + g1 + 1);
+        for (uint64_t& o : rebased) o -= offsets[g0];
+        // (the host vectors are pageable: a write has returned when the device holds the data)
+        d_offsets.Write(queue_, Gs + 1, rebased.data());
+        d_members.Write(queue_, Ms, members.data() + offsets[g0]);
+        rc = ammsb_cover_match(&pi_->Get(), threshold, d_offsets(), Gs, d_members(), Ms, d_dsize(), d_tbest(), d_tover(),
+                               d_ts(), d_dbest(), d_dover(), d_skipped(), d_dense(), d_ws(), ws_bytes, queue_.stream());
+        if (rc != AMMSB_OK) throw PostfitError("ammsb_cover_match", rc, ammsb_cover_last_error());
+      } else {  // (the cover match launches nothing for communities without members: their overlap is 0)
+        const hipError_t e = hipMemsetAsync(d_dense(), 0, Gs * K * sizeof(uint32_t), static_cast<hipStream_t>(queue_.stream()));
+        if (e != hipSuccess) throw std::runtime_error(std::string("CoverNMI: memset: ") + hipGetErrorString(e));
+      }
+      rc = ammsb_nmi_accumulate(d_dense(), g0, Gs, N, d_tsize(), G, d_dsize(), static_cast<uint32_t>(K), d_HX(), d_HY(),
+                                d_cX(), d_cY(), queue_.stream());
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_nmi_accumulate", rc, ammsb_nmi_last_error());
+    }
+    d_HX.Read(queue_, G, r->H_truth.data());
+    d_cX.Read(queue_, G, r->h_truth.data());
+  }
+  d_HY.Read(queue_, K, r->H_detected.data());
+  d_cY.Read(queue_, K, r->h_detected.data());
+  queue_.Finish();
+  // the fallback: a community no pair qualifies for (+inf) keeps its own entropy
+  for (uint64_t g = 0; g < G; ++g) r->h_truth[g] = std::min(r->h_truth[g], r->H_truth[g]);
+  for (uint64_t k = 0; k < K; ++k) r->h_detected[k] = std::min(r->h_detected[k], r->H_detected[k]);
+  r->Derive();
+}
+
+bool Learner::WriteCoverNMI(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
+                            Float threshold, uint64_t slab_bytes) {
+  CoverNmi r;
+  CoverNMI(offsets, members, threshold, &r, slab_bytes);
+  char a[40], b[40], c[40];
+  snprintf(a, sizeof(a), "%.17g", static_cast<double>(threshold));
+  snprintf(b, sizeof(b), "%.17g", r.nmi_lfk);
+  snprintf(c, sizeof(c), "%.17g", r.nmi_max);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.H_truth.size() << " " << a << " " << r.skipped << " " << b
+       << " " << c << "\n";
+  for (size_t g = 0; g < r.H_truth.size(); ++g) {
+    snprintf(a, sizeof(a), "%.17g", r.H_truth[g]);
+    snprintf(b, sizeof(b), "%.17g", r.h_truth[g]);
+    *out << "t " << g << " " << r.truth_size[g] << " " << a << " " << b << "\n";
+  }
+  for (size_t k = 0; k < r.H_detected.size(); ++k) {
+    snprintf(a, sizeof(a), "%.17g", r.H_detected[k]);
+    snprintf(b, sizeof(b), "%.17g", r.h_detected[k]);
+    *out << "d " << k << " " << r.detected_size[k] << " " << a << " " << b << "\n";
   }
   return static_cast<bool>(*out);
 }

@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut;
   bool haveCoverThreshold = false;
   double coverThreshold = 0.05;
   bool haveQualityThreshold = false;
@@ -182,6 +182,7 @@ int main(int argc, char** argv) {
              }},
       OptStr("ground-truth", 0, &groundTruth),  // (new, with --cover-match-out) a SNAP cmty file: one community per line; the graph file's own ids with --file, dense ids with --load-data
       OptStr("cover-match-out", 0, &coverMatchOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold skipped f1_truth f1_detected avg_f1`, then `t g size best overlap f1` per ground-truth and `d k size best overlap f1` per detected community
+      OptStr("cover-nmi-out", 0, &coverNmiOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold skipped nmi_lfk nmi_max`, then `t g size H h` per ground-truth and `d k size H h` per detected community (H the entropy, h the conditional entropy given the other cover; %.17g)
       Option{"cover-match-threshold", 0, "0.05 (new, with --ground-truth and --cover-match-out: a node is a member of k iff pi[a, k] >= it)",
              [&](const std::string& v) {
                haveCoverThreshold = true;
@@ -270,8 +271,12 @@ int main(int argc, char** argv) {
   if (haveQualityThreshold && qualityOut.empty()) Fatal("--community-quality-threshold needs --community-quality-out FILE");
   if (!(qualityThreshold >= 0) || !std::isfinite(static_cast<float>(qualityThreshold)))
     Fatal("--community-quality-threshold must be finite and >= 0");
-  if (groundTruth.empty() != coverMatchOut.empty()) Fatal("--ground-truth FILE and --cover-match-out FILE need each other");
-  if (haveCoverThreshold && coverMatchOut.empty()) Fatal("--cover-match-threshold needs --ground-truth FILE and --cover-match-out FILE");
+  if (groundTruth.empty() && !coverMatchOut.empty()) Fatal("--ground-truth FILE and --cover-match-out FILE need each other");
+  if (groundTruth.empty() && !coverNmiOut.empty()) Fatal("--cover-nmi-out FILE needs --ground-truth FILE");
+  if (!groundTruth.empty() && coverMatchOut.empty() && coverNmiOut.empty())
+    Fatal("--ground-truth FILE and --cover-match-out FILE need each other (or --cover-nmi-out FILE)");
+  if (haveCoverThreshold && coverMatchOut.empty() && coverNmiOut.empty())
+    Fatal("--cover-match-threshold needs --ground-truth FILE and --cover-match-out FILE (or --cover-nmi-out FILE)");
   if (!(coverThreshold >= 0) || !std::isfinite(static_cast<float>(coverThreshold)))
     Fatal("--cover-match-threshold must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
@@ -444,6 +449,18 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("cover match: ") + e.what());
+    }
+  }
+  if (!coverNmiOut.empty()) {
+    // every rank holds all of pi: the comparison is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(coverNmiOut);
+        if (!out.good() || !learner.WriteCoverNMI(&out, truthOffsets, truthMembers, static_cast<mcmc::Float>(coverThreshold)))
+          Fatal("cannot write cover NMI " + coverNmiOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("cover NMI: ") + e.what());
     }
   }
   learner.PrintStats();

@@ -1269,6 +1269,44 @@ class Learner:
         return _cover.Match(threshold, tb.cpu().numpy(), u32(to), u32(ts), db.cpu().numpy(), u32(do),
                             size.cpu().numpy(), int(sk.item()), None if ov is None else u32(ov))
 
+    # ---- the overlapping NMI against a ground-truth cover (include/ammsb_nmi.h).  Like the other read-outs: drained
+    # first, local on any rank, no CPU path, and nothing of the iteration is touched.
+    def _nmi(self):
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the cover NMI has no CPU path")
+        if getattr(self, "_cover_nmi", None) is None:
+            self._cover_nmi = self.ops.CoverNMI(self.ctx)
+        return self._cover_nmi
+
+    def CoverNMI(self, truth, threshold=0.05, slab_bytes=256 << 20):
+        """-> _nmi.NMI: the overlapping NMI of the detected cover D_k = {a : pi[a, k] >= threshold} against the
+        ground-truth cover `truth`, in the forms CompareCover takes (a member >= N reads nothing and is counted in
+        .skipped; a node listed twice inside one community is a ValueError: NMI is defined on sets).  The dense overlap
+        is made slab by slab, Gs communities with Gs K 4 <= slab_bytes (Gs >= 1), by the cover match, and folded on the
+        device into H(X_g | Y) and H(Y_k | X); every float comes from the device.  On the host, in float64: nmi_lfk
+        (Lancichinetti, Fortunato, Kertesz) and nmi_max (McDaid, Greene, Hurley), -1 where undefined.  The results do
+        not depend on slab_bytes."""
+        from . import _cover, _nmi
+        threshold = _cover.check_threshold(threshold)
+        offsets, members = _cover.check_cover(truth)
+        _nmi.check_sets(offsets, members)
+        nm, cm = self._nmi(), self._cover()
+        self.drain()
+        N, K, G = self.cfg.N, self.cfg.K, offsets.size - 1
+        size = self._readout().sizes(self.pi, threshold)
+        off = offsets.astype(np.int64)
+        valid = np.concatenate([[0], np.cumsum(members < N, dtype=np.int64)])
+        tsize = (valid[off[1:]] - valid[off[:-1]]).astype(np.uint32)     # t_g: the members < N
+        st = nm.begin(N, tsize, size)
+        rows = max(1, int(slab_bytes) // (4 * K))
+        for g0 in range(0, G, rows):
+            g1 = min(g0 + rows, G)
+            ov = cm.match(self.pi, threshold, (off[g0:g1 + 1] - off[g0]).astype(np.uint64),
+                          members[off[g0]:off[g1]], size, dense=True)[6]
+            nm.accumulate(st, ov, g0)
+        return _nmi.NMI(threshold, tsize, size.cpu().numpy(), members.size - int(valid[-1]), st.H_truth.cpu().numpy(),
+                        st.c_truth.cpu().numpy(), st.H_detected.cpu().numpy(), st.c_detected.cpu().numpy())
+
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
         out("SAMPLING : %.6f (%%%.2f)" % (self.samplingTime, 100 * self.samplingTime / max(self.time, 1e-12)))

@@ -1104,6 +1104,59 @@ class CoverMatch:
         return self.cv.last_kernel_name()
 
 
+class CoverNMI:
+    """The pair pass of the overlapping NMI (include/ammsb_nmi.h): begin() writes the entropies of both covers and
+    presets the running minima, accumulate() folds one slab of the dense overlap that CoverMatch.match(dense=True)
+    gives for a slice of the ground truth.  float64 from the device; a minimum does not depend on the order of arrival,
+    so the results do not depend on the slabs.  Owns nothing but the tensors it returns."""
+
+    class State:
+        """the arrays of one comparison, on the device"""
+
+        def __init__(self, N, truth_size, detected_size, H_truth, H_detected, c_truth, c_detected):
+            self.N, self.truth_size, self.detected_size = N, truth_size, detected_size
+            self.H_truth, self.H_detected, self.c_truth, self.c_detected = H_truth, H_detected, c_truth, c_detected
+
+    def __init__(self, ctx):
+        from . import _nmi
+        self.ctx = ctx
+        self.nm = _nmi
+        self.lib = _nmi.load()
+
+    def begin(self, N, truth_size, detected_size):
+        """truth_size [G] (uint32 bits): a host array or a contiguous int32 device tensor; detected_size: the [K] int64
+        device tensor CommunityReadout.sizes gives.  -> State: H_truth [G], H_detected [K] written, c_truth [G] and
+        c_detected [K] at +inf."""
+        if not torch.is_tensor(truth_size):
+            truth_size = self.ctx.from_numpy(np.ascontiguousarray(truth_size, dtype=np.uint32).reshape(-1))
+        if truth_size.dtype != torch.int32 or truth_size.dim() != 1 or not truth_size.is_contiguous():
+            raise AmmsbError("cover NMI: truth_size must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        if detected_size.dtype != torch.int64 or detected_size.dim() != 1 or not detected_size.is_contiguous():
+            raise AmmsbError("cover NMI: detected_size must be a contiguous [K] int64 device tensor")
+        G, K, c = int(truth_size.numel()), int(detected_size.numel()), self.ctx
+        st = self.State(int(N), truth_size, detected_size, c.empty((G,), torch.float64), c.empty((K,), torch.float64),
+                        c.empty((G,), torch.float64), c.empty((K,), torch.float64))
+        self.nm.check(self.lib.ammsb_nmi_begin(st.N, _ptr(truth_size), G, _ptr(detected_size), K, _ptr(st.H_truth),
+                                               _ptr(st.H_detected), _ptr(st.c_truth), _ptr(st.c_detected), _stream()))
+        return st
+
+    def accumulate(self, st, overlap, g0):
+        """overlap: the [Gs, K] int32 (uint32 bits) device tensor of rows g0 .. g0 + Gs - 1"""
+        K = int(st.detected_size.numel())
+        if overlap.dtype != torch.int32 or overlap.dim() != 2 or int(overlap.shape[1]) != K or not overlap.is_contiguous():
+            raise AmmsbError("cover NMI: overlap must be a contiguous [Gs, K] int32 (uint32 bits) device tensor")
+        Gs = int(overlap.shape[0])
+        if Gs == 0:  # (an empty tensor has no address)
+            return
+        self.nm.check(self.lib.ammsb_nmi_accumulate(_ptr(overlap), int(g0), Gs, st.N, _ptr(st.truth_size),
+                                                    int(st.truth_size.numel()), _ptr(st.detected_size), K,
+                                                    _ptr(st.H_truth), _ptr(st.H_detected), _ptr(st.c_truth),
+                                                    _ptr(st.c_detected), _stream()))
+
+    def kernel_name(self):
+        return self.nm.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
