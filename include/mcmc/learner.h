@@ -142,6 +142,27 @@ class Learner {
   bool WriteCoverNMI(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
                      Float threshold, uint64_t slab_bytes = 256ull << 20);
 
+  // The Omega index (Collins & Dent) of the detected cover against the same kind of ground truth over the pairs of a
+  // universe of nodes (include/ammsb_omega.h): `universe` holds ascending, distinct ids < N (OmegaUniverse makes the two
+  // standard ones).  Integer counts from the device; the score in signed 128-bit integers, their quotient rounded to
+  // double once.  std::invalid_argument on a bad threshold, CSR or universe and on a community
+  // that lists a node twice; std::runtime_error past 65536 ground-truth communities or 4095 memberships of one node.
+  // Waits, reads and perturbs like CompareCover.
+  struct OmegaIndex {
+    uint64_t nodes = 0, skipped = 0, outside = 0;
+    std::vector<uint64_t> agree, detected, truth;  // [L]: pairs by the communities they share
+    double omega = 0, omega_unadjusted = 0;        // NaN where undefined (the index itself can be negative)
+    void Derive();                                 // the two scores from the three histograms and `nodes`
+  };
+  // kind: "covered" (the nodes with at least one member entry < N) or "all"; std::invalid_argument otherwise
+  static std::vector<uint32_t> OmegaUniverse(const std::string& kind, const std::vector<uint32_t>& members, uint64_t N);
+  void CoverOmega(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                  const std::vector<uint32_t>& universe, OmegaIndex* omega, uint64_t launch_pairs = 1ull << 31);
+  // `# N K G threshold universe_n skipped outside omega omega_unadjusted`, then the L lines `j agree detected truth`;
+  // floats printed with %.17g, NaN as `nan`.
+  bool WriteCoverOmega(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
+                       Float threshold, const std::vector<uint32_t>& universe, uint64_t launch_pairs = 1ull << 31);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

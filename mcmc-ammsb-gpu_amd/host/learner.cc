@@ -12,6 +12,7 @@
 #include "ammsb_quality.h"
 #include "ammsb_cover.h"
 #include "ammsb_nmi.h"
+#include "ammsb_omega.h"
 
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,7 @@
 #include <random>
 #include <sstream>
 #include <stdexcept>
+#include <limits>
 #include <string>
 #include <tuple>
 
@@ -1542,6 +1544,183 @@ bool Learner::WriteCoverNMI(std::ostream* out, const std::vector<uint64_t>& offs
     snprintf(b, sizeof(b), "%.17g", r.h_detected[k]);
     *out << "d " << k << " " << r.detected_size[k] << " " << a << " " << b << "\n";
   }
+  return static_cast<bool>(*out);
+}
+
+// ---- the Omega index against a ground-truth cover: libammsb_omega.so
+namespace {
+// num / den (den != 0, both below 2^127 in magnitude) rounded to binary64 once, to nearest even: 64 quotient bits by long division, the rest as a sticky
+// bit.  What Python's int / int gives.
+double RoundedQuotient(__int128 num, __int128 den) {
+  typedef unsigned __int128 u128;
+  if (num == 0) return 0.0;
+  const bool neg = (num < 0) != (den < 0);
+  const u128 a = num < 0 ? -static_cast<u128>(num) : static_cast<u128>(num);
+  const u128 b = den < 0 ? -static_cast<u128>(den) : static_cast<u128>(den);
+  u128 q = a / b, r = a % b;  // (r < b < 2^127: doubling it cannot wrap)
+  int shift = 0;              // q holds floor(a 2^shift / b)
+  bool sticky = false;
+  while (q >> 64) {
+    sticky = sticky || (q & 1);
+    q >>= 1;
+    --shift;
+  }
+  while (!(q >> 63)) {
+    r <<= 1;
+    q <<= 1;
+    if (r >= b) {
+      r -= b;
+      q |= 1;
+    }
+    ++shift;
+  }
+  sticky = sticky || r != 0;
+  uint64_t bits = static_cast<uint64_t>(q), keep = bits >> 11;
+  const uint64_t low = bits & 0x7FF;
+  if (low > 0x400 || (low == 0x400 && (sticky || (keep & 1)))) ++keep;
+  const double v = std::ldexp(static_cast<double>(keep), 11 - shift);  // (keep <= 2^53: exact)
+  return neg ? -v : v;
+}
+}  // namespace
+
+void Learner::OmegaIndex::Derive() {
+  // one formula with _omega.py (include/ammsb_omega.h): exact integers, the quotient rounded once
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  omega = omega_unadjusted = nan;
+  if (nodes < 2) return;
+  typedef __int128 i128;
+  const i128 P = static_cast<i128>(nodes) * (nodes - 1) / 2;
+  i128 Sa = 0, Se = 0;
+  for (size_t j = 0; j < agree.size(); ++j) {
+    Sa += agree[j];
+    Se += static_cast<i128>(detected[j]) * truth[j];
+  }
+  omega_unadjusted = RoundedQuotient(Sa, P);
+  const i128 den = P * P - Se;
+  if (den != 0) omega = RoundedQuotient(Sa * P - Se, den);
+}
+
+std::vector<uint32_t> Learner::OmegaUniverse(const std::string& kind, const std::vector<uint32_t>& members, uint64_t N) {
+  std::vector<uint32_t> u;
+  if (kind == "all") {
+    u.resize(N);
+    for (uint64_t a = 0; a < N; ++a) u[a] = static_cast<uint32_t>(a);
+  } else if (kind == "covered") {
+    for (uint32_t m : members)
+      if (m < N) u.push_back(m);
+    std::sort(u.begin(), u.end());
+    u.erase(std::unique(u.begin(), u.end()), u.end());
+  } else {
+    throw std::invalid_argument("OmegaUniverse: the universe is \"covered\" or \"all\", not \"" + kind + "\"");
+  }
+  return u;
+}
+
+void Learner::CoverOmega(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                         const std::vector<uint32_t>& universe, OmegaIndex* r, uint64_t launch_pairs) {
+  if (!(threshold >= 0 && std::isfinite(threshold)))
+    throw std::invalid_argument("CoverOmega: the threshold must be finite and >= 0");
+  if (offsets.empty() || offsets.front() != 0 || offsets.back() != members.size() ||
+      !std::is_sorted(offsets.begin(), offsets.end()))
+    throw std::invalid_argument("CoverOmega: offsets must ascend from 0 to the number of members");
+  const uint64_t G = offsets.size() - 1, M = members.size(), K = pi_->Cols(), N = pi_->Rows(), n = universe.size();
+  if ((G >> 31) || (M >> 32)) throw std::invalid_argument("CoverOmega: 2^31 communities or 2^32 members, or more");
+  if (launch_pairs < 1) throw std::invalid_argument("CoverOmega: launch_pairs must be at least 1");
+  for (uint64_t i = 0; i < n; ++i)
+    if (universe[i] >= N || (i > 0 && universe[i] <= universe[i - 1]))
+      throw std::invalid_argument("CoverOmega: the universe ids must ascend, be distinct and < N");
+  {  // the Omega index is defined on sets
+    std::vector<uint32_t> sorted;
+    for (uint64_t g = 0; g < G; ++g) {
+      sorted.assign(members.begin() + offsets[g], members.begin() + offsets[g + 1]);
+      std::sort(sorted.begin(), sorted.end());
+      if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        throw std::invalid_argument("CoverOmega: ground-truth community " + std::to_string(g) +
+                                    " lists a node twice (the Omega index is defined on sets)");
+    }
+  }
+  if (G > AMMSB_OMEGA_MAX_TRUTH) throw std::runtime_error("CoverOmega: more than 65536 ground-truth communities");
+  if (K == 0 || K > AMMSB_OMEGA_MAX_COLS) throw std::runtime_error("CoverOmega: K outside 1..8192");
+  DrainAsync();
+  r->nodes = n;
+  r->skipped = r->outside = 0;
+  uint64_t L = 1;
+  std::vector<uint64_t> hist(4, 0);
+  if (n > 0) {
+    const clcuda::Context context = queue_.GetContext();
+    hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
+    const uint64_t WD = (K + 31) / 32, WT = (G + 31) / 32;
+    std::vector<int32_t> position(N, -1);
+    for (uint64_t i = 0; i < n; ++i) position[universe[i]] = static_cast<int32_t>(i);
+    clcuda::Buffer<uint32_t> d_nodes(context, n), d_dbits(context, n * WD), d_tbits(context, std::max<uint64_t>(n * WT, 1));
+    clcuda::Buffer<uint32_t> d_dcount(context, n), d_tcount(context, n), d_members(context, std::max<uint64_t>(M, 1));
+    clcuda::Buffer<int32_t> d_position(context, N);
+    clcuda::Buffer<uint64_t> d_offsets(context, G + 1), d_tally(context, 2);
+    // (the host vectors are pageable: a write has returned when the device holds the data)
+    d_nodes.Write(queue_, n, universe.data());
+    d_position.Write(queue_, N, position.data());
+    d_offsets.Write(queue_, G + 1, offsets.data());
+    if (M) d_members.Write(queue_, M, members.data());
+    hipError_t e = hipMemsetAsync(d_tbits(), 0, std::max<uint64_t>(n * WT, 1) * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tcount(), 0, n * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tally(), 0, 2 * sizeof(uint64_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("CoverOmega: memset: ") + hipGetErrorString(e));
+    int rc = ammsb_omega_detected_bits(&pi_->Get(), threshold, d_nodes(), n, d_dbits(), d_dcount(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_detected_bits", rc, ammsb_omega_last_error());
+    rc = ammsb_omega_truth_bits(d_offsets(), G, d_members(), M, N, d_position(), n, d_tbits(), d_tcount(), d_tally(),
+                                d_tally() + 1, stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_truth_bits", rc, ammsb_omega_last_error());
+    std::vector<uint32_t> dcount(n), tcount(n);
+    std::vector<uint64_t> tally(2);
+    d_dcount.Read(queue_, n, dcount.data());
+    d_tcount.Read(queue_, n, tcount.data());
+    d_tally.Read(queue_, 2, tally.data());
+    queue_.Finish();
+    r->skipped = tally[0];
+    r->outside = tally[1];
+    L = 1 + std::max<uint64_t>(*std::max_element(dcount.begin(), dcount.end()),
+                               *std::max_element(tcount.begin(), tcount.end()));
+    if (L > AMMSB_OMEGA_MAX_LEVELS) throw std::runtime_error("CoverOmega: a node of the universe is in more than 4095 communities");
+    hist.assign(3 * L + 1, 0);
+    clcuda::Buffer<uint64_t> d_hist(context, 3 * L + 1);
+    e = hipMemsetAsync(d_hist(), 0, (3 * L + 1) * sizeof(uint64_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("CoverOmega: memset: ") + hipGetErrorString(e));
+    const uint64_t R = (n + AMMSB_OMEGA_TILE - 1) / AMMSB_OMEGA_TILE, total = R * (R + 1) / 2;
+    const uint64_t step = std::min<uint64_t>(
+        AMMSB_OMEGA_MAX_LAUNCH_TILES, std::max<uint64_t>(1, launch_pairs / (uint64_t(AMMSB_OMEGA_TILE) * AMMSB_OMEGA_TILE)));
+    for (uint64_t t0 = 0; t0 < total; t0 += step) {
+      rc = ammsb_omega_pairs(d_dbits(), static_cast<uint32_t>(K), d_tbits(), G, n, static_cast<uint32_t>(L), t0,
+                             std::min(step, total - t0), d_hist(), stream);
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_pairs", rc, ammsb_omega_last_error());
+    }
+    d_hist.Read(queue_, 3 * L + 1, hist.data());
+    queue_.Finish();
+    if (hist[3 * L] != 0) throw std::runtime_error("CoverOmega: pairs past the highest level any node reaches");
+  } else {
+    for (uint32_t m : members) r->skipped += m >= N, r->outside += m < N;
+  }
+  r->agree.assign(hist.begin(), hist.begin() + L);
+  r->detected.assign(hist.begin() + L, hist.begin() + 2 * L);
+  r->truth.assign(hist.begin() + 2 * L, hist.begin() + 3 * L);
+  r->Derive();
+}
+
+bool Learner::WriteCoverOmega(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
+                              Float threshold, const std::vector<uint32_t>& universe, uint64_t launch_pairs) {
+  OmegaIndex r;
+  CoverOmega(offsets, members, threshold, universe, &r, launch_pairs);
+  const auto g17 = [](double x, char (&buf)[40]) {
+    if (x != x) snprintf(buf, sizeof(buf), "nan");
+    else snprintf(buf, sizeof(buf), "%.17g", x);
+  };
+  char a[40], b[40], c[40];
+  g17(static_cast<double>(threshold), a);
+  g17(r.omega, b);
+  g17(r.omega_unadjusted, c);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << offsets.size() - 1 << " " << a << " " << r.nodes << " "
+       << r.skipped << " " << r.outside << " " << b << " " << c << "\n";
+  for (size_t j = 0; j < r.agree.size(); ++j)
+    *out << j << " " << r.agree[j] << " " << r.detected[j] << " " << r.truth[j] << "\n";
   return static_cast<bool>(*out);
 }
 

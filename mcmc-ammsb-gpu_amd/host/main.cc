@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse;
   bool haveCoverThreshold = false;
   double coverThreshold = 0.05;
   bool haveQualityThreshold = false;
@@ -183,6 +183,8 @@ int main(int argc, char** argv) {
       OptStr("ground-truth", 0, &groundTruth),  // (new, with --cover-match-out) a SNAP cmty file: one community per line; the graph file's own ids with --file, dense ids with --load-data
       OptStr("cover-match-out", 0, &coverMatchOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold skipped f1_truth f1_detected avg_f1`, then `t g size best overlap f1` per ground-truth and `d k size best overlap f1` per detected community
       OptStr("cover-nmi-out", 0, &coverNmiOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold skipped nmi_lfk nmi_max`, then `t g size H h` per ground-truth and `d k size H h` per detected community (H the entropy, h the conditional entropy given the other cover; %.17g)
+      OptStr("cover-omega-out", 0, &coverOmegaOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold universe_n skipped outside omega omega_unadjusted`, then `j agree detected truth` per level: the pairs of the universe that share j communities (%.17g, `nan` where undefined)
+      OptStr("cover-omega-universe", 0, &coverOmegaUniverse),  // (new, with --cover-omega-out) covered (default: the nodes some ground-truth community holds) | all
       Option{"cover-match-threshold", 0, "0.05 (new, with --ground-truth and --cover-match-out: a node is a member of k iff pi[a, k] >= it)",
              [&](const std::string& v) {
                haveCoverThreshold = true;
@@ -273,10 +275,14 @@ int main(int argc, char** argv) {
     Fatal("--community-quality-threshold must be finite and >= 0");
   if (groundTruth.empty() && !coverMatchOut.empty()) Fatal("--ground-truth FILE and --cover-match-out FILE need each other");
   if (groundTruth.empty() && !coverNmiOut.empty()) Fatal("--cover-nmi-out FILE needs --ground-truth FILE");
-  if (!groundTruth.empty() && coverMatchOut.empty() && coverNmiOut.empty())
-    Fatal("--ground-truth FILE and --cover-match-out FILE need each other (or --cover-nmi-out FILE)");
-  if (haveCoverThreshold && coverMatchOut.empty() && coverNmiOut.empty())
-    Fatal("--cover-match-threshold needs --ground-truth FILE and --cover-match-out FILE (or --cover-nmi-out FILE)");
+  if (groundTruth.empty() && !coverOmegaOut.empty()) Fatal("--cover-omega-out FILE needs --ground-truth FILE");
+  if (!groundTruth.empty() && coverMatchOut.empty() && coverNmiOut.empty() && coverOmegaOut.empty())
+    Fatal("--ground-truth FILE and --cover-match-out FILE need each other (or --cover-nmi-out FILE, or --cover-omega-out FILE)");
+  if (haveCoverThreshold && coverMatchOut.empty() && coverNmiOut.empty() && coverOmegaOut.empty())
+    Fatal("--cover-match-threshold needs --ground-truth FILE and --cover-match-out FILE (or --cover-nmi-out FILE, or --cover-omega-out FILE)");
+  if (!coverOmegaUniverse.empty() && coverOmegaOut.empty()) Fatal("--cover-omega-universe needs --cover-omega-out FILE");
+  if (!coverOmegaUniverse.empty() && coverOmegaUniverse != "covered" && coverOmegaUniverse != "all")
+    Fatal("--cover-omega-universe must be covered or all");
   if (!(coverThreshold >= 0) || !std::isfinite(static_cast<float>(coverThreshold)))
     Fatal("--cover-match-threshold must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
@@ -461,6 +467,21 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("cover NMI: ") + e.what());
+    }
+  }
+  if (!coverOmegaOut.empty()) {
+    // every rank holds all of pi: the comparison is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        const std::vector<uint32_t> universe = mcmc::Learner::OmegaUniverse(
+            coverOmegaUniverse.empty() ? "covered" : coverOmegaUniverse, truthMembers, cfg.N);
+        std::ofstream out(coverOmegaOut);
+        if (!out.good() ||
+            !learner.WriteCoverOmega(&out, truthOffsets, truthMembers, static_cast<mcmc::Float>(coverThreshold), universe))
+          Fatal("cannot write cover Omega " + coverOmegaOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("cover Omega: ") + e.what());
     }
   }
   learner.PrintStats();

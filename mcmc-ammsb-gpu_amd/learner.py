@@ -1307,6 +1307,64 @@ class Learner:
         return _nmi.NMI(threshold, tsize, size.cpu().numpy(), members.size - int(valid[-1]), st.H_truth.cpu().numpy(),
                         st.c_truth.cpu().numpy(), st.H_detected.cpu().numpy(), st.c_detected.cpu().numpy())
 
+    # ---- the Omega index against a ground-truth cover (include/ammsb_omega.h).  Like the other read-outs: drained
+    # first, local on any rank, no CPU path, and nothing of the iteration is touched.
+    def _omega(self):
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the cover Omega index has no CPU path")
+        if getattr(self, "_cover_omega", None) is None:
+            self._cover_omega = self.ops.CoverOmega(self.ctx)
+        return self._cover_omega
+
+    def CoverOmega(self, truth, threshold=0.05, universe="covered", launch_pairs=1 << 31, max_bytes=4 << 30):
+        """-> _omega.Omega: the Omega index (Collins & Dent) of the detected cover D(a) = {k : pi[a, k] >= threshold}
+        against the ground-truth cover `truth`, in the forms CompareCover takes, over the pairs of a universe of nodes:
+        "all", "covered" (the nodes with at least one valid ground-truth membership) or an ascending array of distinct
+        ids < N.  A member >= N is counted in .skipped, a valid member outside the universe in .outside; a node listed
+        twice inside one community is a ValueError.  Per level j the pairs that share j communities in both covers
+        alike (.agree), in the detected cover (.detected) and in the ground truth (.truth), counted on the device, at
+        most launch_pairs pairs per launch; the score in exact integers on the host (.omega, NaN where undefined).  The
+        two bit matrices, n (ceil(K / 32) + ceil(G / 32)) 4 bytes, must fit max_bytes.  The results do not depend on
+        launch_pairs."""
+        from . import _cover, _omega
+        threshold = _cover.check_threshold(threshold)
+        offsets, members = _cover.check_cover(truth)
+        _omega.check_sets(offsets, members)
+        N, K, G = self.cfg.N, self.cfg.K, offsets.size - 1
+        U = _omega.check_universe(universe, N, members)
+        n = int(U.size)
+        if G > _omega.MAX_TRUTH:
+            raise AmmsbError("cover omega: %d ground-truth communities; the bit rows hold at most %d" % (G, _omega.MAX_TRUTH))
+        need = n * ((K + 31) // 32 + (G + 31) // 32) * 4
+        if need > int(max_bytes):
+            raise AmmsbError("cover omega: the bit rows of %d nodes take %d bytes, more than max_bytes = %d; "
+                             "universe=\"covered\" keeps only the nodes the ground truth holds" % (n, need, int(max_bytes)))
+        if int(launch_pairs) < 1:
+            raise AmmsbError("cover omega: launch_pairs must be at least 1")
+        om = self._omega()
+        self.drain()
+        c = self.ctx
+        position = np.full(N, -1, dtype=np.int32)
+        position[U] = np.arange(n, dtype=np.int32)
+        nodes = c.from_numpy(U) if n else None
+        dbits, dcount = om.detected_bits(self.pi, threshold, nodes=nodes, n=n)
+        tbits, tcount, tally = om.truth_bits(c.from_numpy(offsets), c.from_numpy(members), N, c.from_numpy(position), n)
+        L = 1 + (max(int(dcount.max().item()), int(tcount.max().item())) if n else 0)
+        if L > _omega.MAX_LEVELS:
+            raise AmmsbError("cover omega: a node of the universe is in %d communities; the pair pass counts up to %d"
+                             % (L - 1, _omega.MAX_LEVELS - 1))
+        hist = c.zeros((3 * L + 1,), torch.int64)
+        total = _omega.tiles(n)
+        step = min(_omega.MAX_LAUNCH_TILES, max(1, int(launch_pairs) // (_omega.TILE * _omega.TILE)))
+        for t0 in range(0, total, step):
+            om.pairs(dbits, K, tbits, G, n, L, hist, t0, min(step, total - t0))
+        h, tally = hist.cpu().numpy(), tally.cpu().numpy()
+        if n == 0:   # (nothing walked the CSR: every member is skipped or outside, as mcmc::Learner::CoverOmega counts)
+            tally = np.array([int((members >= N).sum()), int((members < N).sum())], dtype=np.int64)
+        if int(h[3 * L]):
+            raise AmmsbError("cover omega: %d pairs at or past level %d, which no node reaches" % (int(h[3 * L]), L))
+        return _omega.Omega(threshold, n, h[:L], h[L:2 * L], h[2 * L:3 * L], int(tally[0]), int(tally[1]), K, G)
+
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
         out("SAMPLING : %.6f (%%%.2f)" % (self.samplingTime, 100 * self.samplingTime / max(self.time, 1e-12)))

@@ -1157,6 +1157,58 @@ class CoverNMI:
         return self.nm.last_kernel_name()
 
 
+class CoverOmega:
+    """The node-pair pass of the Omega index (include/ammsb_omega.h): bit rows of both covers over a universe of nodes,
+    then per pair of positions the communities shared in each cover, as three histograms.  Integer counts over binary32
+    compares: exact, and independent of how the tile range is cut into launches.  Owns nothing but the tensors it
+    returns."""
+
+    def __init__(self, ctx):
+        from . import _omega
+        self.ctx = ctx
+        self.om = _omega
+        self.lib = _omega.load()
+
+    def detected_bits(self, pi, thr, nodes=None, n=None):
+        """nodes: [n] int32 (uint32 bits) device tensor, or None for rows 0 .. n - 1 -> (bits [n, ceil(K / 32)] int32,
+        counts [n] int32) on the device"""
+        n = int(nodes.numel()) if nodes is not None else int(pi.desc.num_rows if n is None else n)
+        W = (int(pi.cols) + 31) // 32
+        bits, counts = self.ctx.empty((n, W), torch.int32), self.ctx.empty((n,), torch.int32)
+        if n:  # (an empty tensor has no address)
+            self.om.check(self.lib.ammsb_omega_detected_bits(C.byref(pi.desc), float(thr), _ptr(nodes), n, _ptr(bits),
+                                                             _ptr(counts), _stream()))
+        return bits, counts
+
+    def truth_bits(self, offsets, members, N, position, n):
+        """offsets [G + 1] int64 (uint64 bits), members [M] int32 (uint32 bits), position [N] int32: device tensors
+        -> (bits [n, ceil(G / 32)] int32, counts [n] int32, tally [2] int64 = skipped, outside) on the device"""
+        G, M, n = int(offsets.numel()) - 1, int(members.numel()), int(n)
+        if G > self.om.MAX_TRUTH:
+            raise AmmsbError("cover omega: %d ground-truth communities; the bit rows hold at most %d (a sparse "
+                             "representation of the ground truth is not built)" % (G, self.om.MAX_TRUTH))
+        c = self.ctx
+        bits, counts = c.zeros((n, (G + 31) // 32), torch.int32), c.zeros((n,), torch.int32)
+        tally = c.zeros((2,), torch.int64)
+        if n and G:
+            self.om.check(self.lib.ammsb_omega_truth_bits(_ptr(offsets), G, _ptr(members) if M else None, M, int(N),
+                                                          _ptr(position), n, _ptr(bits), _ptr(counts), _ptr(tally),
+                                                          C.c_void_p(tally.data_ptr() + 8), _stream()))
+        return bits, counts, tally
+
+    def pairs(self, dbits, K, tbits, G, n, L, hist, tile_begin, tile_count):
+        """adds tiles tile_begin .. tile_begin + tile_count - 1 to hist [3 L + 1] int64"""
+        if hist.dtype != torch.int64 or hist.numel() != 3 * int(L) + 1 or not hist.is_contiguous():
+            raise AmmsbError("cover omega: hist must be a contiguous [3 L + 1] int64 device tensor")
+        if int(n) == 0 or int(tile_count) == 0:
+            return
+        self.om.check(self.lib.ammsb_omega_pairs(_ptr(dbits), int(K), _ptr(tbits) if int(G) else None, int(G), int(n),
+                                                 int(L), int(tile_begin), int(tile_count), _ptr(hist), _stream()))
+
+    def kernel_name(self):
+        return self.om.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
