@@ -5,6 +5,8 @@ There is no CPU fallback: if the shared object is missing or a call fails, this 
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AMMSB_HIP_LIB") or os.path.join(_HERE, "libammsb_hip.so")  # override: A/B runs of two builds
 
@@ -139,10 +141,52 @@ def bind_library(path, signatures, what=""):
     return lib
 
 
-def raise_for(rc, prefix, detail):
-    """AmmsbError for a non-zero return code of one of the post-fit libraries; detail() is its last_error text"""
-    if rc != 0:
-        raise AmmsbError("%s call failed: %d (%s)" % (prefix, rc, detail().decode()))
+class PostfitLibrary:
+    """One of the libraries beside libammsb_hip.so (libammsb_<stem>.so, include/ammsb_<stem>.h), each with a signature
+    table of its own: name -> (restype, argtypes).  The path is AMMSB_<STEM>_LIB or the file next to this module; the
+    library is opened at the first load().  A wrapper module takes its LIB_PATH, load, check and last_kernel_name from
+    here."""
+
+    def __init__(self, stem, signatures):
+        self.stem, self.signatures = stem, signatures
+        self.path = os.environ.get("AMMSB_%s_LIB" % stem.upper()) or os.path.join(_HERE, "libammsb_%s.so" % stem)
+        self._lib = None
+
+    def load(self):
+        """dlopen the library and bind every symbol its header declares"""
+        if self._lib is None:
+            self._lib = bind_library(self.path, self.signatures)
+        return self._lib
+
+    def _call(self, name):
+        return getattr(self.load(), "ammsb_%s_%s" % (self.stem, name))()
+
+    def check(self, rc):
+        """AmmsbError for a non-zero return code, with the library's last_error text"""
+        if rc != 0:
+            raise AmmsbError("ammsb_%s call failed: %d (%s)" % (self.stem, rc, self._call("last_error").decode()))
+
+    def last_kernel_name(self):
+        return self._call("last_kernel_name").decode()
+
+
+def check_threshold(threshold, what):
+    """-> the membership threshold as the libraries take it: a finite binary32 >= 0 (`what` opens the message)"""
+    threshold = float(threshold)
+    if not (0.0 <= threshold <= float(np.finfo(np.float32).max)):   # (a NaN fails both comparisons)
+        raise AmmsbError("%s: the threshold must be finite and >= 0, not %r" % (what, threshold))
+    return float(np.float32(threshold))
+
+
+def _g9(x):
+    """a binary32 as the text files print it"""
+    return "%.9g" % float(x)
+
+
+def _g17(x):
+    """a binary64 as the text files print it: parses back to the same bits; NaN as `nan`"""
+    x = float(x)
+    return "nan" if x != x else "%.17g" % x
 
 
 def load(path=None):

@@ -3,14 +3,11 @@ detected ones and back -- and the host-side helpers that need no device: the der
 means), the SNAP `cmty` reader and writer, and the cover-match text file.  A signature table of its own:
 _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from ._capi import AmmsbError, Rpm, bind_library, raise_for
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_COVER_LIB") or os.path.join(_HERE, "libammsb_cover.so")
+from . import _capi
+from ._capi import AmmsbError, PostfitLibrary, Rpm, _g9
 
 MAX_COLS = 8192    # AMMSB_COVER_MAX_COLS
 UNIT = 128         # AMMSB_COVER_UNIT
@@ -30,31 +27,13 @@ SIGNATURES = {
 # every kernel the dispatcher of csrc/ammsb_cover.hip can launch: the two counting forms and the two finishing passes
 KERNEL_FORMS = ("cover_fast", "cover_generic", "cover_finish", "cover_unpack")
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_cover.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
-
-
-def check(rc):
-    raise_for(rc, "ammsb_cover", load().ammsb_cover_last_error)
-
-
-def last_kernel_name():
-    return load().ammsb_cover_last_kernel_name().decode()
+_LIBRARY = PostfitLibrary("cover", SIGNATURES)
+LIB_PATH, load, check, last_kernel_name = _LIBRARY.path, _LIBRARY.load, _LIBRARY.check, _LIBRARY.last_kernel_name
 
 
 def check_threshold(threshold):
     """-> the threshold as the library takes it: a finite binary32 >= 0"""
-    threshold = float(threshold)
-    if not (0.0 <= threshold <= float(np.finfo(np.float32).max)):   # (a NaN fails both comparisons)
-        raise AmmsbError("cover match: the threshold must be finite and >= 0, not %r" % (threshold,))
-    return float(np.float32(threshold))
+    return _capi.check_threshold(threshold, "cover match")
 
 
 def check_cover(truth):
@@ -85,6 +64,22 @@ def check_cover(truth):
     if offsets.size - 1 >= 1 << 31 or members.size >= 1 << 32:
         raise AmmsbError("cover match: 2^31 communities or 2^32 members, or more")
     return offsets, members
+
+
+def check_sets(offsets, members, what, why):
+    """ValueError if a community of the cover (offsets [G + 1], members [M], as check_cover returns them) lists a node
+    twice: `what` opens the message, `why` is the measure that is defined on sets"""
+    offsets, members = np.asarray(offsets).astype(np.int64), np.asarray(members).astype(np.int64)
+    if members.size < 2:
+        return
+    # sort by (community, member): a duplicate is two equal neighbours of one community
+    comm = np.repeat(np.arange(offsets.size - 1, dtype=np.int64), np.diff(offsets))
+    order = np.lexsort((members, comm))
+    c, m = comm[order], members[order]
+    twice = np.flatnonzero((c[1:] == c[:-1]) & (m[1:] == m[:-1]))
+    if twice.size:
+        raise ValueError("%s: ground-truth community %d lists node %d twice (%s is defined on sets)"
+                         % (what, int(c[twice[0]]), int(m[twice[0]]), why))
 
 
 # ---------------------------------------------------------------------------------------------- derived measures
@@ -204,10 +199,6 @@ def write_cover(path, offsets, members):
 
 
 # ---------------------------------------------------------------------------------------------- the cover-match file
-def _g9(x):
-    return "%.9g" % float(x)
-
-
 def write_cover_match(path, N, m):
     """A Match as a text file, byte for byte what mcmc::Learner::WriteCoverMatch writes: `# N K G threshold skipped
     f1_truth f1_detected avg_f1`, then the G lines `t g size best overlap f1` and the K lines `d k size best overlap f1`.  Floats

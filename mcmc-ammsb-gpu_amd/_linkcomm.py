@@ -2,14 +2,10 @@
 largest terms (pi[a,k] * pi[b,k]) * beta_k of its probability -- and the host-side helpers that need no device (the
 link-communities text file).  A signature table of its own: _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from ._capi import AmmsbError, Rpm, bind_library, raise_for
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_LINKCOMM_LIB") or os.path.join(_HERE, "libammsb_linkcomm.so")
+from ._capi import AmmsbError, PostfitLibrary, Rpm, _g9
 
 MAX_TOP = 16       # AMMSB_LINKCOMM_MAX_TOP
 MAX_COLS = 8192    # AMMSB_LINKCOMM_MAX_COLS
@@ -29,23 +25,8 @@ SIGNATURES = {
 KERNEL_FORMS = ("linkcomm_fast_v1", "linkcomm_fast_v2", "linkcomm_fast_v4", "linkcomm_fast_v4_chunked",
                 "linkcomm_generic")
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_linkcomm.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
-
-
-def check(rc):
-    raise_for(rc, "ammsb_linkcomm", load().ammsb_linkcomm_last_error)
-
-
-def last_kernel_name():
-    return load().ammsb_linkcomm_last_kernel_name().decode()
+_LIBRARY = PostfitLibrary("linkcomm", SIGNATURES)
+LIB_PATH, load, check, last_kernel_name = _LIBRARY.path, _LIBRARY.load, _LIBRARY.check, _LIBRARY.last_kernel_name
 
 
 def check_args(top, min_term):
@@ -57,10 +38,6 @@ def check_args(top, min_term):
     if not (0.0 <= min_term <= float(np.finfo(np.float32).max)):   # (a NaN fails both comparisons)
         raise AmmsbError("link communities: min_term must be finite and >= 0, not %r" % (min_term,))
     return top, float(np.float32(min_term))
-
-
-def _g9(x):
-    return "%.9g" % float(x)
 
 
 def write_link_communities(path, N, K, top, min_term, edges, prob, ids, terms):

@@ -2,14 +2,10 @@
 node from a fitted (pi, beta) on the device, and the host-side helpers that need no device (the AUC rank statistic, the
 predicted-links text file).  A signature table of its own: _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from ._capi import AmmsbError, Rpm, SetDesc, bind_library, raise_for
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_LINKPRED_LIB") or os.path.join(_HERE, "libammsb_linkpred.so")
+from ._capi import AmmsbError, PostfitLibrary, Rpm, SetDesc
 
 MAX_TOP = 64       # AMMSB_LINKPRED_MAX_TOP
 MAX_COLS = 8192    # AMMSB_LINKPRED_MAX_COLS
@@ -34,23 +30,8 @@ SIGNATURES = {
 KERNEL_FORMS = tuple("linkpred_%s_mfma_%s_%s" % (e, q, v) for e in ("block", "top") for q in ("q128", "q32")
                      for v in ("v4", "v1")) + ("linkpred_pairs_v4", "linkpred_pairs_v1")
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_linkpred.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
-
-
-def check(rc):
-    raise_for(rc, "ammsb_linkpred", load().ammsb_linkpred_last_error)
-
-
-def last_kernel_name():
-    return load().ammsb_linkpred_last_kernel_name().decode()
+_LIBRARY = PostfitLibrary("linkpred", SIGNATURES)
+LIB_PATH, load, check, last_kernel_name = _LIBRARY.path, _LIBRARY.load, _LIBRARY.check, _LIBRARY.last_kernel_name
 
 
 def check_top(top):

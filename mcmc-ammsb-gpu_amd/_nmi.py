@@ -3,14 +3,11 @@ against a ground-truth cover -- and the host-side helpers that need no device: t
 the two scores from the entropies, and the cover-NMI text file.  A signature table of its own: _capi.SIGNATURES mirrors
 include/ammsb.h and nothing else."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from ._capi import AmmsbError, bind_library, raise_for
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_NMI_LIB") or os.path.join(_HERE, "libammsb_nmi.so")
+from . import _cover
+from ._capi import AmmsbError, PostfitLibrary, _g17
 
 MAX_COLS = 8192    # AMMSB_NMI_MAX_COLS
 
@@ -27,39 +24,13 @@ SIGNATURES = {
 # every kernel the dispatchers of csrc/ammsb_nmi.hip can launch
 KERNEL_FORMS = ("nmi_begin", "nmi_fast", "nmi_generic")
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_nmi.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
-
-
-def check(rc):
-    raise_for(rc, "ammsb_nmi", load().ammsb_nmi_last_error)
-
-
-def last_kernel_name():
-    return load().ammsb_nmi_last_kernel_name().decode()
+_LIBRARY = PostfitLibrary("nmi", SIGNATURES)
+LIB_PATH, load, check, last_kernel_name = _LIBRARY.path, _LIBRARY.load, _LIBRARY.check, _LIBRARY.last_kernel_name
 
 
 def check_sets(offsets, members):
-    """NMI is defined on sets: ValueError if a community of the cover (offsets [G + 1], members [M], as
-    _cover.check_cover returns them) lists a node twice"""
-    offsets, members = np.asarray(offsets).astype(np.int64), np.asarray(members).astype(np.int64)
-    if members.size < 2:
-        return
-    # sort by (community, member): a duplicate is two equal neighbours of one community
-    comm = np.repeat(np.arange(offsets.size - 1, dtype=np.int64), np.diff(offsets))
-    order = np.lexsort((members, comm))
-    c, m = comm[order], members[order]
-    twice = np.flatnonzero((c[1:] == c[:-1]) & (m[1:] == m[:-1]))
-    if twice.size:
-        raise ValueError("cover NMI: ground-truth community %d lists node %d twice (NMI is defined on sets)"
-                         % (int(c[twice[0]]), int(m[twice[0]])))
+    """NMI is defined on sets: ValueError if a community of the cover lists a node twice"""
+    _cover.check_sets(offsets, members, "cover NMI", "NMI")
 
 
 # ---------------------------------------------------------------------------------------------- the two scores
@@ -115,10 +86,6 @@ class NMI:
 
 
 # ---------------------------------------------------------------------------------------------- the cover-NMI file
-def _g17(x):
-    return "%.17g" % float(x)
-
-
 def write_cover_nmi(path, N, r):
     """An NMI as a text file, byte for byte what mcmc::Learner::WriteCoverNMI writes: `# N K G threshold skipped nmi_lfk
     nmi_max`, then the G lines `t g size H h` and the K lines `d k size H h`.  Floats are printed with %.17g, which

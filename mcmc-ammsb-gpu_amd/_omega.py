@@ -4,14 +4,11 @@ cover is made of sets, the score from the three histograms in exact integers, an
 signature table of its own: _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 
-from ._capi import AmmsbError, Rpm, bind_library, raise_for
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_OMEGA_LIB") or os.path.join(_HERE, "libammsb_omega.so")
+from . import _cover
+from ._capi import AmmsbError, PostfitLibrary, Rpm, _g17
 
 MAX_COLS = 8192                  # AMMSB_OMEGA_MAX_COLS
 MAX_TRUTH = 65536                # AMMSB_OMEGA_MAX_TRUTH
@@ -33,23 +30,8 @@ SIGNATURES = {
 # every kernel the dispatchers of csrc/ammsb_omega.hip can launch
 KERNEL_FORMS = ("omega_bits_fast", "omega_bits_generic", "omega_truth_scatter", "omega_truth_count", "omega_pairs")
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_omega.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
-
-
-def check(rc):
-    raise_for(rc, "ammsb_omega", load().ammsb_omega_last_error)
-
-
-def last_kernel_name():
-    return load().ammsb_omega_last_kernel_name().decode()
+_LIBRARY = PostfitLibrary("omega", SIGNATURES)
+LIB_PATH, load, check, last_kernel_name = _LIBRARY.path, _LIBRARY.load, _LIBRARY.check, _LIBRARY.last_kernel_name
 
 
 def tiles(n):
@@ -59,18 +41,8 @@ def tiles(n):
 
 
 def check_sets(offsets, members):
-    """The Omega index is defined on sets: ValueError if a community of the cover (offsets [G + 1], members [M], as
-    _cover.check_cover returns them) lists a node twice"""
-    offsets, members = np.asarray(offsets).astype(np.int64), np.asarray(members).astype(np.int64)
-    if members.size < 2:
-        return
-    comm = np.repeat(np.arange(offsets.size - 1, dtype=np.int64), np.diff(offsets))
-    order = np.lexsort((members, comm))
-    c, m = comm[order], members[order]
-    twice = np.flatnonzero((c[1:] == c[:-1]) & (m[1:] == m[:-1]))
-    if twice.size:
-        raise ValueError("cover omega: ground-truth community %d lists node %d twice (the Omega index is defined on sets)"
-                         % (int(c[twice[0]]), int(m[twice[0]])))
+    """The Omega index is defined on sets: ValueError if a community of the cover lists a node twice"""
+    _cover.check_sets(offsets, members, "cover omega", "the Omega index")
 
 
 def check_universe(universe, N, members):
@@ -138,11 +110,6 @@ class Omega:
 
 
 # ---------------------------------------------------------------------------------------------- the cover-Omega file
-def _g17(x):
-    x = float(x)
-    return "nan" if x != x else "%.17g" % x
-
-
 def write_cover_omega(path, N, r):
     """An Omega as a text file, byte for byte what mcmc::Learner::WriteCoverOmega writes: `# N K G threshold universe_n
     skipped outside omega omega_unadjusted`, then the L lines `j agree detected truth`.  Floats are printed with %.17g,

@@ -3,14 +3,11 @@ leave it, from one membership bit per (node, community) -- and the host-side hel
 measures (conductance, density, coverage) and the community-quality text file.  A signature table of its own:
 _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from ._capi import AmmsbError, Rpm, bind_library, raise_for
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_QUALITY_LIB") or os.path.join(_HERE, "libammsb_quality.so")
+from . import _capi
+from ._capi import AmmsbError, PostfitLibrary, Rpm, _g9
 
 MAX_COLS = 8192    # AMMSB_QUALITY_MAX_COLS
 
@@ -29,31 +26,13 @@ SIGNATURES = {
 # every kernel form the dispatchers of csrc/ammsb_quality.hip can select
 KERNEL_FORMS = ("quality_mask_fast", "quality_mask_generic", "quality_edges_w1", "quality_edges_w2")
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_quality.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
-
-
-def check(rc):
-    raise_for(rc, "ammsb_quality", load().ammsb_quality_last_error)
-
-
-def last_kernel_name():
-    return load().ammsb_quality_last_kernel_name().decode()
+_LIBRARY = PostfitLibrary("quality", SIGNATURES)
+LIB_PATH, load, check, last_kernel_name = _LIBRARY.path, _LIBRARY.load, _LIBRARY.check, _LIBRARY.last_kernel_name
 
 
 def check_threshold(threshold):
     """-> the threshold as the library takes it: a finite binary32 >= 0"""
-    threshold = float(threshold)
-    if not (0.0 <= threshold <= float(np.finfo(np.float32).max)):   # (a NaN fails both comparisons)
-        raise AmmsbError("community quality: the threshold must be finite and >= 0, not %r" % (threshold,))
-    return float(np.float32(threshold))
+    return _capi.check_threshold(threshold, "community quality")
 
 
 def conductance(internal, boundary, links):
@@ -97,10 +76,6 @@ class Quality:
     def __repr__(self):
         return "Quality(K=%d, links=%d, uncovered=%d, skipped=%d, coverage=%.6g)" % (
             self.size.size, self.links, self.uncovered, self.skipped, self.coverage)
-
-
-def _g9(x):
-    return "%.9g" % float(x)
 
 
 def write_community_quality(path, N, threshold, size, internal, boundary, links, uncovered):

@@ -2,14 +2,10 @@
 device, and the host-side helpers that need no device (the community CSR built from an ids table, the communities text
 file).  A signature table of its own: _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from ._capi import AmmsbError, Rpm, bind_library, raise_for
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_READOUT_LIB") or os.path.join(_HERE, "libammsb_readout.so")
+from ._capi import AmmsbError, PostfitLibrary, Rpm
 
 MAX_TOP = 16       # AMMSB_READOUT_MAX_TOP
 MAX_COLS = 8192    # AMMSB_READOUT_MAX_COLS
@@ -25,23 +21,8 @@ SIGNATURES = {
     "ammsb_readout_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_readout.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
-
-
-def check(rc):
-    raise_for(rc, "ammsb_readout", load().ammsb_readout_last_error)
-
-
-def last_kernel_name():
-    return load().ammsb_readout_last_kernel_name().decode()
+_LIBRARY = PostfitLibrary("readout", SIGNATURES)
+LIB_PATH, load, check, last_kernel_name = _LIBRARY.path, _LIBRARY.load, _LIBRARY.check, _LIBRARY.last_kernel_name
 
 
 def check_args(top, threshold):

@@ -2,12 +2,8 @@
 device, and the host helpers it rests on (rand_r jump-ahead, the unordered_set epoch table).  A signature table of its
 own: _capi.SIGNATURES mirrors include/ammsb.h and nothing else."""
 import ctypes as C
-import os
 
-from ._capi import AmmsbError, SetDesc, bind_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AMMSB_REFSAMPLE_LIB") or os.path.join(_HERE, "libammsb_refsample.so")
+from ._capi import AmmsbError, PostfitLibrary, SetDesc
 
 STRATEGIES = {"Node": 0, "NodeLink": 1, "NodeNonLink": 2}
 
@@ -35,15 +31,8 @@ SIGNATURES = {
     "ammsb_refsample_link": (C.c_int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
 }
 
-_lib = None
-
-
-def load():
-    """dlopen the library and bind every symbol include/ammsb_refsample.h declares"""
-    global _lib
-    if _lib is None:
-        _lib = bind_library(LIB_PATH, SIGNATURES)
-    return _lib
+_LIBRARY = PostfitLibrary("refsample", SIGNATURES)   # (no check / last_kernel_name: its errors belong to a sampler handle)
+LIB_PATH, load = _LIBRARY.path, _LIBRARY.load
 
 
 def rand_r(state):

@@ -67,10 +67,6 @@ __device__ __forceinline__ bool ratio_gt(uint32_t o1, u64 s1, uint32_t o2, u64 s
   return lh > rh || (lh == rh && ll > rl);
 }
 
-__device__ __forceinline__ uint32_t col_of(bool fast, uint32_t j, uint32_t lane) {
-  return fast ? 256u * (j >> 2) + 4u * lane + (j & 3u) : 64u * j + lane;
-}
-
 // the community that holds entry p < M: the largest g with offsets[g] <= p
 __device__ __forceinline__ uint32_t community_of(const CoverArgs& a, u64 p) {
   uint32_t lo = 0, hi = a.G;
@@ -112,7 +108,7 @@ __device__ __forceinline__ void finish_community(const CoverArgs& a, uint32_t g,
   for (uint32_t j = 0; j < a.W; ++j) {
     const uint32_t o = get(j);
     if (o) {
-      const uint32_t col = col_of(fast, j, lane);
+      const uint32_t col = slot_col(fast, j, lane);
       if (col < K) {  // (a count can only be of a column)
         const u64 d = a.dsize[col], s = (u64)t + d;
         if (a.dense) a.dense[(u64)g * K + col] = o;

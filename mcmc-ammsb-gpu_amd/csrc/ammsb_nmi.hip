@@ -75,7 +75,7 @@ __global__ __launch_bounds__(N_BLOCK) void nmi_begin(u64 N, const uint32_t* tsiz
 
 template <bool FAST>
 __device__ __forceinline__ uint32_t col_of(uint32_t ch, int j, uint32_t lane) {
-  return ch * CHUNK + (FAST ? 256u * (uint32_t)(j >> 2) + 4u * lane + (uint32_t)(j & 3) : 64u * (uint32_t)j + lane);
+  return ch * CHUNK + slot_col(FAST, (uint32_t)j, lane);
 }
 
 // the lane's 16 entries of one row of one chunk; a slot past the row holds 0

@@ -46,14 +46,6 @@ struct BitsArgs {
   uint32_t* counts;  // [n]
 };
 
-// ballot t of the row goes to lane t & 63, into its first (t < 64) or second register
-__device__ __forceinline__ void place(u64& w0, u64& w1, uint32_t t, u64 b, int lane) {
-  if (lane == (int)(t & 63u)) {
-    if (t < 64u) w0 = b;
-    else w1 = b;
-  }
-}
-
 // lane l holds ballots l and l + 64: words 2 l, 2 l + 1 and 128 + 2 l, 128 + 2 l + 1 of the row
 __device__ __forceinline__ void store_row(const BitsArgs& a, u64 p, uint32_t W, u64 w0, u64 w1, uint32_t cnt, int lane) {
   uint32_t* out = a.bits + p * W;
@@ -109,7 +101,7 @@ __global__ __launch_bounds__(O_BLOCK) void omega_bits_generic(BitsArgs a) {
     if (ok) {
       const float* src = postfit_row(a.pi, row);
       for (uint32_t t = 0; t < B; ++t) {
-        const uint32_t col = t < F ? 256u * (t >> 2) + 4u * lane + (t & 3u) : 64u * t + lane;
+        const uint32_t col = slot_col(t < F, t, (uint32_t)lane);
         const float v = col < K ? src[col] : -1.0f;  // (below every threshold the entry point lets through)
         const u64 b = __ballot(v >= a.thr);
         cnt += (uint32_t)__popcll(b);

@@ -1,7 +1,7 @@
-// What the libraries that read a fitted model share (libammsb_readout / _linkpred / _linkcomm / _quality / _cover .so): the
-// descriptor check that decides whether a kernel may issue 16-byte loads, the per-thread error and launch state, the
-// wave-wide selection the exactness claims of DESIGN 4.8 and 4.10 rest on, the block-private counters and the row
-// addressing.
+// What the libraries that read a fitted model share (libammsb_readout / _linkpred / _linkcomm / _quality / _cover / _nmi /
+// _omega .so): the descriptor check that decides whether a kernel may issue 16-byte loads, the per-thread error and
+// launch state, the wave-wide selection the exactness claims of DESIGN 4.8 and 4.10 rest on, the block-private
+// counters, the row addressing, and the slot -> column rule of the kernels that read a row either way.
 //
 // Everything here has internal linkage on purpose (an unnamed namespace; device code is __forceinline__): each
 // library is one translation unit, keeps thread_local state of its own and exports nothing but what its header
@@ -25,6 +25,22 @@ __device__ __forceinline__ const float* postfit_row(const ammsb_rpm& m, uint32_t
   const uint32_t rib = (uint32_t)m.rows_in_block;
   const uint32_t blk = row / rib;
   return reinterpret_cast<const float*>(m.blocks[blk]) + (uint64_t)(row - blk * rib) * m.num_cols;
+}
+
+// Which column slot j of lane `lane` stands for, in a kernel whose lanes walk a row (or 64 j-aligned part of one) in
+// slots.  The 16-byte form loads float4 number j >> 2 of the lane and takes its component j & 3; the generic form reads
+// one element per slot, lanes side by side.  Both forms of a library write the same words, so its readers use this too.
+__device__ __forceinline__ uint32_t slot_col(bool fast, uint32_t j, uint32_t lane) {
+  return fast ? 256u * (j >> 2) + 4u * lane + (j & 3u) : 64u * j + lane;
+}
+
+// ballot (or word) t of a bit row goes to lane t & 63, into its first (t < 64) or second register
+__device__ __forceinline__ void place(unsigned long long& w0, unsigned long long& w1, uint32_t t, unsigned long long bits,
+                                      int lane) {
+  if (lane == (int)(t & 63u)) {
+    if (t < 64u) w0 = bits;
+    else w1 = bits;
+  }
 }
 
 // ------------------------------------------------------------------------------------------ host: errors, launches

@@ -36,14 +36,6 @@ struct MaskArgs {
   u64* mask;
 };
 
-// word t of the row goes to lane t & 63, into its first (t < 64) or second register
-__device__ __forceinline__ void place(u64& w0, u64& w1, uint32_t t, u64 bits, int lane) {
-  if (lane == (int)(t & 63u)) {
-    if (t < 64u) w0 = bits;
-    else w1 = bits;
-  }
-}
-
 __device__ __forceinline__ void store_row(const MaskArgs& a, uint64_t row, uint32_t W, u64 w0, u64 w1, int lane) {
   u64* out = a.mask + row * W;
   if ((uint32_t)lane < W) out[lane] = w0;
@@ -95,7 +87,7 @@ __global__ __launch_bounds__(Q_BLOCK) void quality_mask_generic(MaskArgs a) {
     const float* p = postfit_row(a.pi, (uint32_t)r);
     u64 w0 = 0, w1 = 0;
     for (uint32_t t = 0; t < W; ++t) {
-      const uint32_t col = t < F ? 256u * (t >> 2) + 4u * lane + (t & 3u) : 64u * t + lane;
+      const uint32_t col = slot_col(t < F, t, (uint32_t)lane);
       const float v = col < K ? p[col] : -1.0f;
       place(w0, w1, t, __ballot(v >= a.thr), lane);
     }
@@ -115,7 +107,7 @@ struct EdgeArgs {
 };
 
 __device__ __forceinline__ uint32_t col_of(uint32_t w, uint32_t j, uint32_t F) {
-  return w < F ? 256u * (w >> 2) + 4u * j + (w & 3u) : 64u * w + j;
+  return slot_col(w < F, w, j);
 }
 
 template <int WPL>

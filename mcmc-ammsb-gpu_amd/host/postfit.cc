@@ -1,0 +1,686 @@
+// mcmc::Learner's post-fit analyses (include/mcmc/learner.h): what reads a fitted model out -- memberships and
+// communities, link prediction, link communities, community quality, and the three comparisons with a ground-truth cover
+// (F1 match, overlapping NMI, Omega index).  Each is a thin driver of one library of its own (libammsb_readout.so ...
+// libammsb_omega.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
+// read the results back, and for the Write* methods print them.  Nothing here touches the training loop of learner.cc.
+#include "mcmc/learner.h"
+#include "ammsb_readout.h"
+#include "ammsb_linkpred.h"
+#include "ammsb_linkcomm.h"
+#include "ammsb_quality.h"
+#include "ammsb_cover.h"
+#include "ammsb_nmi.h"
+#include "ammsb_omega.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <stdexcept>
+#include <string>
+
+namespace mcmc {
+
+namespace {
+// what a failed call of one of the post-fit libraries throws: its return code in words and the library's own detail
+std::runtime_error PostfitError(const char* call, int rc, const char* detail) {
+  return std::runtime_error(std::string(call) + ": " + ammsb_strerror(rc) + " (" + detail + ")");
+}
+
+// the membership threshold of the analyses that compare pi with it on the device (Memberships has a looser rule)
+void CheckThreshold(const char* who, Float threshold) {
+  if (!(threshold >= 0 && std::isfinite(threshold)))
+    throw std::invalid_argument(std::string(who) + ": the threshold must be finite and >= 0");
+}
+
+// a ground-truth cover as (offsets, members): G + 1 ascending offsets into the member list, within the libraries' ranges
+void CheckTruthCover(const char* who, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members) {
+  if (offsets.empty() || offsets.front() != 0 || offsets.back() != members.size() ||
+      !std::is_sorted(offsets.begin(), offsets.end()))
+    throw std::invalid_argument(std::string(who) + ": offsets must ascend from 0 to the number of members");
+  if (((offsets.size() - 1) >> 31) || (static_cast<uint64_t>(members.size()) >> 32))
+    throw std::invalid_argument(std::string(who) + ": 2^31 communities or 2^32 members, or more");
+}
+
+// no ground-truth community lists a node twice; `what` is the measure that is defined on sets
+void CheckSets(const char* who, const char* what, const std::vector<uint64_t>& offsets,
+               const std::vector<uint32_t>& members) {
+  std::vector<uint32_t> sorted;
+  for (size_t g = 0; g + 1 < offsets.size(); ++g) {
+    sorted.assign(members.begin() + offsets[g], members.begin() + offsets[g + 1]);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+      throw std::invalid_argument(std::string(who) + ": ground-truth community " + std::to_string(g) +
+                                  " lists a node twice (" + what + " is defined on sets)");
+  }
+}
+
+// a number as the output files hold it: %.9g for what is a float, %.17g for what is a double, "nan" without a sign
+std::string Num(double x, int digits) {
+  if (x != x) return "nan";
+  char buf[40];
+  snprintf(buf, sizeof(buf), "%.*g", digits, x);
+  return buf;
+}
+std::string G9(double x) { return Num(x, 9); }
+std::string G17(double x) { return Num(x, 17); }
+}  // namespace
+
+// ---- reading the model out: libammsb_readout.so over pi, in row slabs whose outputs stay under a fixed byte budget
+void Learner::Memberships(uint32_t top, Float threshold, std::vector<uint32_t>* ids, std::vector<Float>* weights,
+                          std::vector<uint32_t>* count, std::vector<uint64_t>* sizes) {
+  if (top == 0 || top > AMMSB_READOUT_MAX_TOP) throw std::invalid_argument("Memberships: top must be in 1..16");
+  if (!(threshold >= 0)) throw std::invalid_argument("Memberships: the threshold must be >= 0");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  const bool tops = ids || weights || count;
+  const uint64_t slab = std::min<uint64_t>(std::max<uint64_t>(N, 1), (64ull << 20) / (8ull * top + 4));
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint32_t> d_ids(context, tops ? slab * top : 1), d_count(context, tops ? slab : 1);
+  clcuda::Buffer<Float> d_weights(context, tops ? slab * top : 1);
+  std::unique_ptr<clcuda::Buffer<uint64_t>> d_sizes;
+  if (sizes) {
+    sizes->assign(K, 0);
+    d_sizes.reset(new clcuda::Buffer<uint64_t>(context, queue_, sizes->begin(), sizes->end()));
+  }
+  if (ids) ids->resize(N * top);
+  if (weights) weights->resize(N * top);
+  if (count) count->resize(N);
+  for (uint64_t lo = 0; lo < N; lo += slab) {
+    const uint64_t n = std::min(slab, N - lo);
+    const int rc = ammsb_readout_top(&pi_->Get(), nullptr, lo, n, top, threshold, tops ? d_ids() : nullptr,
+                                     tops ? d_weights() : nullptr, tops ? d_count() : nullptr,
+                                     d_sizes ? (*d_sizes)() : nullptr, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw PostfitError("ammsb_readout_top", rc, ammsb_readout_last_error());
+    if (ids) d_ids.Read(queue_, n * top, ids->data() + lo * top);
+    if (weights) d_weights.Read(queue_, n * top, weights->data() + lo * top);
+    if (count) d_count.Read(queue_, n, count->data() + lo);
+  }
+  if (sizes) d_sizes->Read(queue_, K, sizes->data());
+  queue_.Finish();
+}
+
+void Learner::Communities(uint32_t top, Float threshold, std::vector<uint64_t>* offsets, std::vector<uint32_t>* members,
+                          std::vector<uint64_t>* sizes) {
+  std::vector<uint32_t> ids;
+  Memberships(top, threshold, &ids, nullptr, nullptr, sizes);
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  offsets->assign(K + 1, 0);
+  for (uint32_t id : ids)
+    if (id != AMMSB_READOUT_NONE) ++(*offsets)[id + 1];
+  for (uint64_t k = 0; k < K; ++k) (*offsets)[k + 1] += (*offsets)[k];
+  members->assign((*offsets)[K], 0);
+  std::vector<uint64_t> fill(offsets->begin(), offsets->end() - 1);
+  for (uint64_t a = 0; a < N; ++a)  // ascending nodes, so every community's list comes out ascending
+    for (uint32_t t = 0; t < top; ++t) {
+      const uint32_t id = ids[a * top + t];
+      if (id != AMMSB_READOUT_NONE) (*members)[fill[id]++] = static_cast<uint32_t>(a);
+    }
+}
+
+bool Learner::WriteCommunities(std::ostream* out, uint32_t top, Float threshold) {
+  std::vector<uint64_t> offsets, sizes;
+  std::vector<uint32_t> members;
+  Communities(top, threshold, &offsets, &members, &sizes);
+  const uint64_t K = pi_->Cols();
+  *out << "# " << pi_->Rows() << " " << K << " " << top << " " << G9(threshold) << "\n";
+  for (uint64_t k = 0; k < K; ++k) {
+    *out << k << " " << sizes[k];
+    for (uint64_t i = offsets[k]; i < offsets[k + 1]; ++i) *out << " " << members[i];
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- predicting links: libammsb_linkpred.so over (pi, beta), eps as the kernels hold it (MakeKernelParams)
+void Learner::LinkProbabilities(const std::vector<Edge>& edges, std::vector<Float>* out) {
+  DrainAsync();
+  queue_.Finish();
+  out->assign(edges.size(), 0);
+  if (edges.empty()) return;
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Edge> d_edges(context, queue_, edges.begin(), edges.end());
+  clcuda::Buffer<Float> d_out(context, edges.size());
+  const int rc = ammsb_linkpred_pairs(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), edges.size(),
+                                      d_out(), queue_.stream());
+  if (rc != AMMSB_OK)
+    throw PostfitError("ammsb_linkpred_pairs", rc, ammsb_linkpred_last_error());
+  d_out.Read(queue_, edges.size(), out->data());
+  queue_.Finish();
+}
+
+void Learner::PredictLinks(const std::vector<Vertex>& nodes, uint32_t top, uint32_t exclude_mask,
+                           std::vector<Vertex>* ids, std::vector<Float>* scores) {
+  if (top == 0 || top > AMMSB_LINKPRED_MAX_TOP) throw std::invalid_argument("PredictLinks: top must be in 1..64");
+  if (exclude_mask & ~(kExcludeTraining | kExcludeHeldout)) throw std::invalid_argument("PredictLinks: unknown exclude bits");
+  const uint64_t N = pi_->Rows(), K = pi_->Cols(), Q = nodes.size();
+  for (Vertex v : nodes)
+    if (v >= N) throw std::invalid_argument("PredictLinks: a node id >= N");
+  DrainAsync();
+  queue_.Finish();
+  ids->assign(Q * top, AMMSB_LINKPRED_NONE);
+  scores->assign(Q * top, 0);
+  if (Q == 0) return;
+  const ammsb_set* ex[2] = {nullptr, nullptr};
+  int n_ex = 0;
+  if (exclude_mask & kExcludeTraining) ex[n_ex++] = &trainingSet_->Get();
+  if ((exclude_mask & kExcludeHeldout) && heldoutSet_) ex[n_ex++] = &heldoutSet_->Get();
+  // whole tiles of 128 queries whose outputs stay under a fixed byte budget; the workspace does not grow with Q
+  const uint64_t slab = std::min<uint64_t>(Q, std::max<uint64_t>(128, (64ull << 20) / (8ull * top) / 128 * 128));
+  const uint64_t ws_bytes = ammsb_linkpred_top_workspace_bytes(static_cast<uint32_t>(slab), top, N, K);
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Vertex> d_nodes(context, queue_, nodes.begin(), nodes.end()), d_ids(context, slab * top);
+  clcuda::Buffer<Float> d_scores(context, slab * top);
+  clcuda::Buffer<uint64_t> d_ws(context, (ws_bytes + 7) / 8);
+  const Float eps = MakeKernelParams(cfg_).epsilon;
+  for (uint64_t lo = 0; lo < Q; lo += slab) {
+    const uint64_t n = std::min(slab, Q - lo);
+    const int rc = ammsb_linkpred_top(&pi_->Get(), beta_.data(), eps, d_nodes() + lo, static_cast<uint32_t>(n), top, ex[0],
+                                      ex[1], 0, N, d_ids(), d_scores(), d_ws(), ws_bytes, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw PostfitError("ammsb_linkpred_top", rc, ammsb_linkpred_last_error());
+    d_ids.Read(queue_, n * top, ids->data() + lo * top);
+    d_scores.Read(queue_, n * top, scores->data() + lo * top);
+  }
+  queue_.Finish();
+}
+
+bool Learner::WritePredictedLinks(std::ostream* out, const std::vector<Vertex>& nodes, uint32_t top,
+                                  uint32_t exclude_mask) {
+  std::vector<Vertex> ids;
+  std::vector<Float> scores;
+  PredictLinks(nodes, top, exclude_mask, &ids, &scores);
+  static const char* const kNames[4] = {"none", "training", "heldout", "all"};
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << top << " " << kNames[exclude_mask & 3u] << "\n";
+  for (size_t i = 0; i < nodes.size(); ++i) {
+    uint32_t n = 0;
+    while (n < top && ids[i * top + n] != AMMSB_LINKPRED_NONE) ++n;
+    *out << nodes[i] << " " << n;
+    for (uint32_t t = 0; t < n; ++t) *out << " " << ids[i * top + t] << " " << G9(scores[i * top + t]);
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- the communities that explain a link: libammsb_linkcomm.so over (pi, beta), eps as the kernels hold it
+namespace {
+void CheckLinkCommArgs(const char* who, uint32_t top, Float min_term) {
+  if (top == 0 || top > AMMSB_LINKCOMM_MAX_TOP) throw std::invalid_argument(std::string(who) + ": top must be in 1..16");
+  if (!(min_term >= 0 && std::isfinite(min_term)))
+    throw std::invalid_argument(std::string(who) + ": min_term must be finite and >= 0");
+}
+
+// every training link once, ascending ((min << 32) | max is how an Edge is stored)
+std::vector<Edge> SortedTrainingLinks(const Config& cfg) {
+  std::vector<Edge> links(cfg.training_edges.begin(), cfg.training_edges.end());
+  std::sort(links.begin(), links.end());
+  links.erase(std::unique(links.begin(), links.end()), links.end());
+  return links;
+}
+}  // namespace
+
+void Learner::LinkCommunities(const std::vector<Edge>& edges, uint32_t top, Float min_term, std::vector<uint32_t>* ids,
+                              std::vector<Float>* terms, std::vector<Float>* prob) {
+  CheckLinkCommArgs("LinkCommunities", top, min_term);
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t n_all = edges.size();
+  ids->assign(n_all * top, AMMSB_LINKCOMM_NONE);
+  terms->assign(n_all * top, 0);
+  prob->assign(n_all, 0);
+  if (n_all == 0) return;
+  const uint64_t slab = std::min<uint64_t>(n_all, std::max<uint64_t>(1, (64ull << 20) / (8ull * top + 4)));
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Edge> d_edges(context, queue_, edges.begin(), edges.end());
+  clcuda::Buffer<uint32_t> d_ids(context, slab * top);
+  clcuda::Buffer<Float> d_terms(context, slab * top), d_prob(context, slab);
+  const Float eps = MakeKernelParams(cfg_).epsilon;
+  for (uint64_t lo = 0; lo < n_all; lo += slab) {
+    const uint64_t n = std::min(slab, n_all - lo);
+    const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), eps, d_edges() + lo, n, top, min_term, d_ids(),
+                                        d_terms(), d_prob(), nullptr, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw PostfitError("ammsb_linkcomm_edges", rc, ammsb_linkcomm_last_error());
+    d_ids.Read(queue_, n * top, ids->data() + lo * top);
+    d_terms.Read(queue_, n * top, terms->data() + lo * top);
+    d_prob.Read(queue_, n, prob->data() + lo);
+  }
+  queue_.Finish();
+}
+
+void Learner::LinkCommunitySizes(Float min_term, std::vector<uint64_t>* sizes) {
+  CheckLinkCommArgs("LinkCommunitySizes", 1, min_term);
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t K = pi_->Cols();
+  sizes->assign(K + 1, 0);
+  const std::vector<Edge> links = SortedTrainingLinks(cfg_);
+  if (links.empty()) return;
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<Edge> d_edges(context, queue_, links.begin(), links.end());
+  clcuda::Buffer<uint64_t> d_sizes(context, queue_, sizes->begin(), sizes->end());
+  const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), links.size(), 1,
+                                      min_term, nullptr, nullptr, nullptr, d_sizes(), queue_.stream());
+  if (rc != AMMSB_OK)
+    throw PostfitError("ammsb_linkcomm_edges", rc, ammsb_linkcomm_last_error());
+  d_sizes.Read(queue_, K + 1, sizes->data());
+  queue_.Finish();
+}
+
+bool Learner::WriteLinkCommunities(std::ostream* out, uint32_t top, Float min_term) {
+  const std::vector<Edge> links = SortedTrainingLinks(cfg_);
+  std::vector<uint32_t> ids;
+  std::vector<Float> terms, prob;
+  LinkCommunities(links, top, min_term, &ids, &terms, &prob);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << links.size() << " " << top << " " << G9(min_term) << "\n";
+  for (size_t i = 0; i < links.size(); ++i) {
+    uint32_t n = 0;
+    while (n < top && ids[i * top + n] != AMMSB_LINKCOMM_NONE) ++n;
+    *out << (links[i] >> 32) << " " << (links[i] & 0xFFFFFFFFull) << " " << G9(prob[i]) << " " << n;
+    for (uint32_t t = 0; t < n; ++t) *out << " " << ids[i * top + t] << " " << G9(terms[i * top + t]);
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- scoring communities against the graph: libammsb_quality.so over pi and the training links
+void Learner::CommunityQuality(Float threshold, std::vector<uint64_t>* size, std::vector<uint64_t>* internal,
+                               std::vector<uint64_t>* boundary, uint64_t* uncovered) {
+  CheckThreshold("CommunityQuality", threshold);
+  Memberships(1, threshold, nullptr, nullptr, nullptr, size);  // (drains; sizes only)
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  internal->assign(K, 0);
+  boundary->assign(K, 0);
+  *uncovered = 0;
+  const std::vector<Edge> links = SortedTrainingLinks(cfg_);
+  if (links.empty() || N == 0) return;
+  const uint64_t words = ammsb_quality_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
+  if (words == 0) throw std::runtime_error("CommunityQuality: K outside 1..8192");
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint64_t> d_mask(context, words);
+  clcuda::Buffer<Edge> d_edges(context, queue_, links.begin(), links.end());
+  std::vector<uint64_t> counts(2 * K + 2, 0);
+  clcuda::Buffer<uint64_t> d_counts(context, queue_, counts.begin(), counts.end());
+  int rc = ammsb_quality_mask(&pi_->Get(), threshold, d_mask(), queue_.stream());
+  if (rc == AMMSB_OK)
+    rc = ammsb_quality_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), links.size(), d_counts(), nullptr,
+                             queue_.stream());
+  if (rc != AMMSB_OK)
+    throw PostfitError("ammsb_quality", rc, ammsb_quality_last_error());
+  d_counts.Read(queue_, 2 * K + 2, counts.data());
+  queue_.Finish();
+  std::copy(counts.begin(), counts.begin() + K, internal->begin());
+  std::copy(counts.begin() + K, counts.begin() + 2 * K, boundary->begin());
+  *uncovered = counts[2 * K];
+}
+
+bool Learner::WriteCommunityQuality(std::ostream* out, Float threshold) {
+  std::vector<uint64_t> size, internal, boundary;
+  uint64_t uncovered = 0;
+  CommunityQuality(threshold, &size, &internal, &boundary, &uncovered);
+  const uint64_t links = SortedTrainingLinks(cfg_).size();  // (a training link has both ends < N: none is skipped)
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << links << " " << G9(threshold) << " " << uncovered << "\n";
+  for (size_t k = 0; k < size.size(); ++k) {
+    // float64, as include/ammsb_quality.h states the measures
+    const uint64_t vol = 2 * internal[k] + boundary[k], low = std::min(vol, 2 * links - vol);
+    const double cond = low ? static_cast<double>(boundary[k]) / static_cast<double>(low) : -1.0;
+    const double sz = static_cast<double>(size[k]);
+    const double dens = size[k] >= 2 ? static_cast<double>(internal[k]) / (sz * (sz - 1.0) / 2.0) : -1.0;
+    *out << k << " " << size[k] << " " << internal[k] << " " << boundary[k] << " " << G9(cond) << " " << G9(dens) << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- matching the detected cover to a ground-truth cover: libammsb_cover.so over pi and the member list
+void Learner::CoverMatch::Derive() {
+  // one formula with _cover.py: F1 = 2 o / (t + d) in float64, the means added in index order
+  const auto each = [](const std::vector<int32_t>& best, const std::vector<uint32_t>& over, auto own, auto other,
+                       std::vector<double>* f1, double* mean) {
+    f1->assign(best.size(), 0.0);
+    double sum = 0;
+    uint64_t present = 0;
+    for (size_t i = 0; i < best.size(); ++i) {
+      if (best[i] >= 0 && over[i] > 0)
+        (*f1)[i] = 2.0 * static_cast<double>(over[i]) / (static_cast<double>(own(i)) + static_cast<double>(other(best[i])));
+      if (own(i) > 0) {
+        sum += (*f1)[i];
+        ++present;
+      }
+    }
+    *mean = present ? sum / static_cast<double>(present) : -1.0;
+  };
+  const auto t = [this](size_t g) { return static_cast<uint64_t>(truth_size[g]); };
+  const auto d = [this](size_t k) { return detected_size[k]; };
+  each(truth_best, truth_overlap, t, d, &f1_truth_each, &f1_truth);
+  each(detected_best, detected_overlap, d, t, &f1_detected_each, &f1_detected);
+  avg_f1 = f1_truth >= 0 && f1_detected >= 0 ? (f1_truth + f1_detected) / 2.0 : -1.0;
+}
+
+void Learner::CompareCover(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                           CoverMatch* m, std::vector<uint32_t>* overlap) {
+  CheckThreshold("CompareCover", threshold);
+  CheckTruthCover("CompareCover", offsets, members);
+  const uint64_t G = offsets.size() - 1, M = members.size(), K = pi_->Cols();
+  Memberships(1, threshold, nullptr, nullptr, nullptr, &m->detected_size);  // (drains; sizes only)
+  m->truth_best.assign(G, -1);
+  m->truth_overlap.assign(G, 0);
+  m->truth_size.assign(G, 0);
+  m->detected_best.assign(K, -1);
+  m->detected_overlap.assign(K, 0);
+  m->skipped = 0;
+  if (overlap) overlap->assign(G * K, 0);
+  if (G > 0 && M > 0) {  // (with nothing to compare the library launches nothing: every community is unmatched)
+    const uint64_t ws_bytes = ammsb_cover_workspace_bytes(M, static_cast<uint32_t>(K));
+    if (ws_bytes == 0) throw std::runtime_error("CompareCover: K outside 1..8192");
+    const clcuda::Context context = queue_.GetContext();
+    clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
+    clcuda::Buffer<uint32_t> d_members(context, queue_, members.begin(), members.end());
+    clcuda::Buffer<uint64_t> d_dsize(context, queue_, m->detected_size.begin(), m->detected_size.end());
+    clcuda::Buffer<int32_t> d_tbest(context, G), d_dbest(context, K);
+    clcuda::Buffer<uint32_t> d_tover(context, G), d_tsize(context, G), d_dover(context, K);
+    clcuda::Buffer<uint32_t> d_dense(context, overlap ? G * K : 1);
+    clcuda::Buffer<uint64_t> d_skipped(context, 1), d_ws(context, (ws_bytes + 7) / 8);
+    const int rc = ammsb_cover_match(&pi_->Get(), threshold, d_offsets(), G, d_members(), M, d_dsize(), d_tbest(),
+                                     d_tover(), d_tsize(), d_dbest(), d_dover(), d_skipped(),
+                                     overlap ? d_dense() : nullptr, d_ws(), ws_bytes, queue_.stream());
+    if (rc != AMMSB_OK)
+      throw PostfitError("ammsb_cover_match", rc, ammsb_cover_last_error());
+    d_tbest.Read(queue_, G, m->truth_best.data());
+    d_tover.Read(queue_, G, m->truth_overlap.data());
+    d_tsize.Read(queue_, G, m->truth_size.data());
+    d_dbest.Read(queue_, K, m->detected_best.data());
+    d_dover.Read(queue_, K, m->detected_overlap.data());
+    d_skipped.Read(queue_, 1, &m->skipped);
+    if (overlap) d_dense.Read(queue_, G * K, overlap->data());
+    queue_.Finish();
+  }
+  m->Derive();
+}
+
+bool Learner::WriteCoverMatch(std::ostream* out, const std::vector<uint64_t>& offsets,
+                              const std::vector<uint32_t>& members, Float threshold) {
+  CoverMatch m;
+  CompareCover(offsets, members, threshold, &m);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << m.truth_best.size() << " " << G9(threshold) << " "
+       << m.skipped << " " << G9(m.f1_truth) << " " << G9(m.f1_detected) << " " << G9(m.avg_f1) << "\n";
+  for (size_t g = 0; g < m.truth_best.size(); ++g)
+    *out << "t " << g << " " << m.truth_size[g] << " " << m.truth_best[g] << " " << m.truth_overlap[g] << " "
+         << G9(m.f1_truth_each[g]) << "\n";
+  for (size_t k = 0; k < m.detected_best.size(); ++k)
+    *out << "d " << k << " " << m.detected_size[k] << " " << m.detected_best[k] << " " << m.detected_overlap[k] << " "
+         << G9(m.f1_detected_each[k]) << "\n";
+  return static_cast<bool>(*out);
+}
+
+// ---- the overlapping NMI against a ground-truth cover: libammsb_cover.so for the dense overlap of a slab,
+// libammsb_nmi.so for the pair pass
+void Learner::CoverNmi::Derive() {
+  // one formula with _nmi.py (include/ammsb_nmi.h), the sums added in index order
+  const auto side = [](const std::vector<double>& H, const std::vector<double>& h, double* mean, double* sumH,
+                       double* sumh) {
+    double ratios = 0;
+    uint64_t present = 0;
+    *sumH = *sumh = 0;
+    for (size_t i = 0; i < H.size(); ++i) {
+      if (H[i] > 0) {
+        ratios += h[i] / H[i];
+        ++present;
+      }
+      *sumH += H[i];
+      *sumh += h[i];
+    }
+    *mean = present ? ratios / static_cast<double>(present) : -1.0;
+  };
+  double mx, my, HX, hX, HY, hY;
+  side(H_truth, h_truth, &mx, &HX, &hX);
+  side(H_detected, h_detected, &my, &HY, &hY);
+  nmi_lfk = mx < 0 || my < 0 ? -1.0 : 1.0 - 0.5 * (mx + my);
+  const double den = std::max(HX, HY);
+  nmi_max = den > 0 ? 0.5 * (HX - hX + HY - hY) / den : -1.0;
+}
+
+void Learner::CoverNMI(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                       CoverNmi* r, uint64_t slab_bytes) {
+  CheckThreshold("CoverNMI", threshold);
+  CheckTruthCover("CoverNMI", offsets, members);
+  const uint64_t G = offsets.size() - 1, K = pi_->Cols(), N = pi_->Rows();
+  CheckSets("CoverNMI", "NMI", offsets, members);
+  Memberships(1, threshold, nullptr, nullptr, nullptr, &r->detected_size);  // (drains; sizes only)
+  r->truth_size.assign(G, 0);
+  r->skipped = 0;
+  for (uint64_t g = 0; g < G; ++g)
+    for (uint64_t i = offsets[g]; i < offsets[g + 1]; ++i) {
+      if (members[i] < N) ++r->truth_size[g];
+      else ++r->skipped;
+    }
+  r->H_truth.assign(G, 0);
+  r->h_truth.assign(G, 0);
+  r->H_detected.assign(K, 0);
+  r->h_detected.assign(K, 0);
+  if (K == 0 || K > AMMSB_NMI_MAX_COLS) throw std::runtime_error("CoverNMI: K outside 1..8192");
+  const clcuda::Context context = queue_.GetContext();
+  const uint64_t rows = std::min<uint64_t>(std::max<uint64_t>(G, 1), std::max<uint64_t>(1, slab_bytes / (4 * K)));
+  uint64_t most_members = 1;  // of a slab
+  for (uint64_t g0 = 0; g0 < G; g0 += rows)
+    most_members = std::max(most_members, offsets[std::min(g0 + rows, G)] - offsets[g0]);
+  const uint64_t ws_bytes = std::max<uint64_t>(8, ammsb_cover_workspace_bytes(most_members, static_cast<uint32_t>(K)));
+  clcuda::Buffer<uint32_t> d_tsize(context, std::max<uint64_t>(G, 1));
+  if (G) d_tsize.Write(queue_, G, r->truth_size.data());
+  clcuda::Buffer<uint64_t> d_dsize(context, queue_, r->detected_size.begin(), r->detected_size.end());
+  clcuda::Buffer<double> d_HX(context, std::max<uint64_t>(G, 1)), d_cX(context, std::max<uint64_t>(G, 1));
+  clcuda::Buffer<double> d_HY(context, K), d_cY(context, K);
+  int rc = ammsb_nmi_begin(N, d_tsize(), G, d_dsize(), static_cast<uint32_t>(K), d_HX(), d_HY(), d_cX(), d_cY(),
+                           queue_.stream());
+  if (rc != AMMSB_OK) throw PostfitError("ammsb_nmi_begin", rc, ammsb_nmi_last_error());
+  if (G > 0) {
+    clcuda::Buffer<uint64_t> d_offsets(context, rows + 1), d_skipped(context, 1), d_ws(context, (ws_bytes + 7) / 8);
+    clcuda::Buffer<uint32_t> d_members(context, most_members), d_dense(context, rows * K);
+    clcuda::Buffer<int32_t> d_tbest(context, rows), d_dbest(context, K);
+    clcuda::Buffer<uint32_t> d_tover(context, rows), d_ts(context, rows), d_dover(context, K);
+    std::vector<uint64_t> rebased;
+    for (uint64_t g0 = 0; g0 < G; g0 += rows) {
+      const uint64_t g1 = std::min(g0 + rows, G), Gs = g1 - g0, Ms = offsets[g1] - offsets[g0];
+      if (Ms > 0) {
+        rebased.assign(offsets.begin() + g0, offsets.begin() + g1 + 1);
+        for (uint64_t& o : rebased) o -= offsets[g0];
+        // (the host vectors are pageable: a write has returned when the device holds the data)
+        d_offsets.Write(queue_, Gs + 1, rebased.data());
+        d_members.Write(queue_, Ms, members.data() + offsets[g0]);
+        rc = ammsb_cover_match(&pi_->Get(), threshold, d_offsets(), Gs, d_members(), Ms, d_dsize(), d_tbest(), d_tover(),
+                               d_ts(), d_dbest(), d_dover(), d_skipped(), d_dense(), d_ws(), ws_bytes, queue_.stream());
+        if (rc != AMMSB_OK) throw PostfitError("ammsb_cover_match", rc, ammsb_cover_last_error());
+      } else {  // (the cover match launches nothing for communities without members: their overlap is 0)
+        const hipError_t e = hipMemsetAsync(d_dense(), 0, Gs * K * sizeof(uint32_t), static_cast<hipStream_t>(queue_.stream()));
+        if (e != hipSuccess) throw std::runtime_error(std::string("CoverNMI: memset: ") + hipGetErrorString(e));
+      }
+      rc = ammsb_nmi_accumulate(d_dense(), g0, Gs, N, d_tsize(), G, d_dsize(), static_cast<uint32_t>(K), d_HX(), d_HY(),
+                                d_cX(), d_cY(), queue_.stream());
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_nmi_accumulate", rc, ammsb_nmi_last_error());
+    }
+    d_HX.Read(queue_, G, r->H_truth.data());
+    d_cX.Read(queue_, G, r->h_truth.data());
+  }
+  d_HY.Read(queue_, K, r->H_detected.data());
+  d_cY.Read(queue_, K, r->h_detected.data());
+  queue_.Finish();
+  // the fallback: a community no pair qualifies for (+inf) keeps its own entropy
+  for (uint64_t g = 0; g < G; ++g) r->h_truth[g] = std::min(r->h_truth[g], r->H_truth[g]);
+  for (uint64_t k = 0; k < K; ++k) r->h_detected[k] = std::min(r->h_detected[k], r->H_detected[k]);
+  r->Derive();
+}
+
+bool Learner::WriteCoverNMI(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
+                            Float threshold, uint64_t slab_bytes) {
+  CoverNmi r;
+  CoverNMI(offsets, members, threshold, &r, slab_bytes);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.H_truth.size() << " " << G17(threshold) << " " << r.skipped
+       << " " << G17(r.nmi_lfk) << " " << G17(r.nmi_max) << "\n";
+  for (size_t g = 0; g < r.H_truth.size(); ++g)
+    *out << "t " << g << " " << r.truth_size[g] << " " << G17(r.H_truth[g]) << " " << G17(r.h_truth[g]) << "\n";
+  for (size_t k = 0; k < r.H_detected.size(); ++k)
+    *out << "d " << k << " " << r.detected_size[k] << " " << G17(r.H_detected[k]) << " " << G17(r.h_detected[k]) << "\n";
+  return static_cast<bool>(*out);
+}
+
+// ---- the Omega index against a ground-truth cover: libammsb_omega.so
+namespace {
+// num / den (den != 0, both below 2^127 in magnitude) rounded to binary64 once, to nearest even: 64 quotient bits by long division, the rest as a sticky
+// bit.  What Python's int / int gives.
+double RoundedQuotient(__int128 num, __int128 den) {
+  typedef unsigned __int128 u128;
+  if (num == 0) return 0.0;
+  const bool neg = (num < 0) != (den < 0);
+  const u128 a = num < 0 ? -static_cast<u128>(num) : static_cast<u128>(num);
+  const u128 b = den < 0 ? -static_cast<u128>(den) : static_cast<u128>(den);
+  u128 q = a / b, r = a % b;  // (r < b < 2^127: doubling it cannot wrap)
+  int shift = 0;              // q holds floor(a 2^shift / b)
+  bool sticky = false;
+  while (q >> 64) {
+    sticky = sticky || (q & 1);
+    q >>= 1;
+    --shift;
+  }
+  while (!(q >> 63)) {
+    r <<= 1;
+    q <<= 1;
+    if (r >= b) {
+      r -= b;
+      q |= 1;
+    }
+    ++shift;
+  }
+  sticky = sticky || r != 0;
+  uint64_t bits = static_cast<uint64_t>(q), keep = bits >> 11;
+  const uint64_t low = bits & 0x7FF;
+  if (low > 0x400 || (low == 0x400 && (sticky || (keep & 1)))) ++keep;
+  const double v = std::ldexp(static_cast<double>(keep), 11 - shift);  // (keep <= 2^53: exact)
+  return neg ? -v : v;
+}
+}  // namespace
+
+void Learner::OmegaIndex::Derive() {
+  // one formula with _omega.py (include/ammsb_omega.h): exact integers, the quotient rounded once
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  omega = omega_unadjusted = nan;
+  if (nodes < 2) return;
+  typedef __int128 i128;
+  const i128 P = static_cast<i128>(nodes) * (nodes - 1) / 2;
+  i128 Sa = 0, Se = 0;
+  for (size_t j = 0; j < agree.size(); ++j) {
+    Sa += agree[j];
+    Se += static_cast<i128>(detected[j]) * truth[j];
+  }
+  omega_unadjusted = RoundedQuotient(Sa, P);
+  const i128 den = P * P - Se;
+  if (den != 0) omega = RoundedQuotient(Sa * P - Se, den);
+}
+
+std::vector<uint32_t> Learner::OmegaUniverse(const std::string& kind, const std::vector<uint32_t>& members, uint64_t N) {
+  std::vector<uint32_t> u;
+  if (kind == "all") {
+    u.resize(N);
+    for (uint64_t a = 0; a < N; ++a) u[a] = static_cast<uint32_t>(a);
+  } else if (kind == "covered") {
+    for (uint32_t m : members)
+      if (m < N) u.push_back(m);
+    std::sort(u.begin(), u.end());
+    u.erase(std::unique(u.begin(), u.end()), u.end());
+  } else {
+    throw std::invalid_argument("OmegaUniverse: the universe is \"covered\" or \"all\", not \"" + kind + "\"");
+  }
+  return u;
+}
+
+void Learner::CoverOmega(const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members, Float threshold,
+                         const std::vector<uint32_t>& universe, OmegaIndex* r, uint64_t launch_pairs) {
+  CheckThreshold("CoverOmega", threshold);
+  CheckTruthCover("CoverOmega", offsets, members);
+  const uint64_t G = offsets.size() - 1, M = members.size(), K = pi_->Cols(), N = pi_->Rows(), n = universe.size();
+  if (launch_pairs < 1) throw std::invalid_argument("CoverOmega: launch_pairs must be at least 1");
+  for (uint64_t i = 0; i < n; ++i)
+    if (universe[i] >= N || (i > 0 && universe[i] <= universe[i - 1]))
+      throw std::invalid_argument("CoverOmega: the universe ids must ascend, be distinct and < N");
+  CheckSets("CoverOmega", "the Omega index", offsets, members);
+  if (G > AMMSB_OMEGA_MAX_TRUTH) throw std::runtime_error("CoverOmega: more than 65536 ground-truth communities");
+  if (K == 0 || K > AMMSB_OMEGA_MAX_COLS) throw std::runtime_error("CoverOmega: K outside 1..8192");
+  DrainAsync();
+  r->nodes = n;
+  r->skipped = r->outside = 0;
+  uint64_t L = 1;
+  std::vector<uint64_t> hist(4, 0);
+  if (n > 0) {
+    const clcuda::Context context = queue_.GetContext();
+    hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
+    const uint64_t WD = (K + 31) / 32, WT = (G + 31) / 32;
+    std::vector<int32_t> position(N, -1);
+    for (uint64_t i = 0; i < n; ++i) position[universe[i]] = static_cast<int32_t>(i);
+    clcuda::Buffer<uint32_t> d_nodes(context, n), d_dbits(context, n * WD), d_tbits(context, std::max<uint64_t>(n * WT, 1));
+    clcuda::Buffer<uint32_t> d_dcount(context, n), d_tcount(context, n), d_members(context, std::max<uint64_t>(M, 1));
+    clcuda::Buffer<int32_t> d_position(context, N);
+    clcuda::Buffer<uint64_t> d_offsets(context, G + 1), d_tally(context, 2);
+    // (the host vectors are pageable: a write has returned when the device holds the data)
+    d_nodes.Write(queue_, n, universe.data());
+    d_position.Write(queue_, N, position.data());
+    d_offsets.Write(queue_, G + 1, offsets.data());
+    if (M) d_members.Write(queue_, M, members.data());
+    hipError_t e = hipMemsetAsync(d_tbits(), 0, std::max<uint64_t>(n * WT, 1) * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tcount(), 0, n * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tally(), 0, 2 * sizeof(uint64_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("CoverOmega: memset: ") + hipGetErrorString(e));
+    int rc = ammsb_omega_detected_bits(&pi_->Get(), threshold, d_nodes(), n, d_dbits(), d_dcount(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_detected_bits", rc, ammsb_omega_last_error());
+    rc = ammsb_omega_truth_bits(d_offsets(), G, d_members(), M, N, d_position(), n, d_tbits(), d_tcount(), d_tally(),
+                                d_tally() + 1, stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_truth_bits", rc, ammsb_omega_last_error());
+    std::vector<uint32_t> dcount(n), tcount(n);
+    std::vector<uint64_t> tally(2);
+    d_dcount.Read(queue_, n, dcount.data());
+    d_tcount.Read(queue_, n, tcount.data());
+    d_tally.Read(queue_, 2, tally.data());
+    queue_.Finish();
+    r->skipped = tally[0];
+    r->outside = tally[1];
+    L = 1 + std::max<uint64_t>(*std::max_element(dcount.begin(), dcount.end()),
+                               *std::max_element(tcount.begin(), tcount.end()));
+    if (L > AMMSB_OMEGA_MAX_LEVELS) throw std::runtime_error("CoverOmega: a node of the universe is in more than 4095 communities");
+    hist.assign(3 * L + 1, 0);
+    clcuda::Buffer<uint64_t> d_hist(context, 3 * L + 1);
+    e = hipMemsetAsync(d_hist(), 0, (3 * L + 1) * sizeof(uint64_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("CoverOmega: memset: ") + hipGetErrorString(e));
+    const uint64_t R = (n + AMMSB_OMEGA_TILE - 1) / AMMSB_OMEGA_TILE, total = R * (R + 1) / 2;
+    const uint64_t step = std::min<uint64_t>(
+        AMMSB_OMEGA_MAX_LAUNCH_TILES, std::max<uint64_t>(1, launch_pairs / (uint64_t(AMMSB_OMEGA_TILE) * AMMSB_OMEGA_TILE)));
+    for (uint64_t t0 = 0; t0 < total; t0 += step) {
+      rc = ammsb_omega_pairs(d_dbits(), static_cast<uint32_t>(K), d_tbits(), G, n, static_cast<uint32_t>(L), t0,
+                             std::min(step, total - t0), d_hist(), stream);
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_pairs", rc, ammsb_omega_last_error());
+    }
+    d_hist.Read(queue_, 3 * L + 1, hist.data());
+    queue_.Finish();
+    if (hist[3 * L] != 0) throw std::runtime_error("CoverOmega: pairs past the highest level any node reaches");
+  } else {
+    for (uint32_t m : members) r->skipped += m >= N, r->outside += m < N;
+  }
+  r->agree.assign(hist.begin(), hist.begin() + L);
+  r->detected.assign(hist.begin() + L, hist.begin() + 2 * L);
+  r->truth.assign(hist.begin() + 2 * L, hist.begin() + 3 * L);
+  r->Derive();
+}
+
+bool Learner::WriteCoverOmega(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
+                              Float threshold, const std::vector<uint32_t>& universe, uint64_t launch_pairs) {
+  OmegaIndex r;
+  CoverOmega(offsets, members, threshold, universe, &r, launch_pairs);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << offsets.size() - 1 << " " << G17(threshold) << " " << r.nodes
+       << " " << r.skipped << " " << r.outside << " " << G17(r.omega) << " " << G17(r.omega_unadjusted) << "\n";
+  for (size_t j = 0; j < r.agree.size(); ++j)
+    *out << j << " " << r.agree[j] << " " << r.detected[j] << " " << r.truth[j] << "\n";
+  return static_cast<bool>(*out);
+}
+
+
+}  // namespace mcmc

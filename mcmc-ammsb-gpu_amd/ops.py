@@ -810,6 +810,24 @@ class ReferenceStreamSampler:
             pass
 
 
+def _edge_keys(ctx, edges, what):
+    """edge keys (a << 32) | b, a host array or a contiguous 1-d int64 (uint64 bits) device tensor -> the device tensor"""
+    if not torch.is_tensor(edges):
+        edges = ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
+    if edges.dtype != torch.int64 or edges.dim() != 1 or not edges.is_contiguous():
+        raise AmmsbError("%s: edges must be a contiguous 1-d int64 (uint64 bits) device tensor" % what)
+    return edges
+
+
+def _u32_vector(ctx, x, what):
+    """uint32 values, a host array or a contiguous 1-d int32 (uint32 bits) device tensor -> the device tensor"""
+    if not torch.is_tensor(x):
+        x = ctx.from_numpy(np.ascontiguousarray(x, dtype=np.uint32).reshape(-1))
+    if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous():
+        raise AmmsbError("%s must be a contiguous 1-d int32 (uint32 bits) device tensor" % what)
+    return x
+
+
 class CommunityReadout:
     """The read-out of a fitted pi (include/ammsb_readout.h): per row the T strongest communities with their weights
     (value descending, equal values by column ascending), the number of columns >= thr, and per community the number of
@@ -875,11 +893,7 @@ class LinkPredictor:
         self.workspace = None
 
     def _nodes(self, nodes):
-        if not torch.is_tensor(nodes):
-            nodes = self.ctx.from_numpy(np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1))
-        if nodes.dtype != torch.int32 or nodes.dim() != 1 or not nodes.is_contiguous():
-            raise AmmsbError("link prediction: nodes must be a contiguous 1-d int32 (uint32 bits) device tensor")
-        return nodes
+        return _u32_vector(self.ctx, nodes, "link prediction: nodes")
 
     def _range(self, pi, cand):
         lo, hi = (0, pi.rows) if cand is None else (int(cand[0]), int(cand[1]))
@@ -927,10 +941,7 @@ class LinkPredictor:
 
     def pairs(self, pi, beta, epsilon, edges):
         """-> [n] float32: p(a, b) per edge key (a << 32 | b, either order of the ends); -1 for an end >= N."""
-        if not torch.is_tensor(edges):
-            edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
-        if edges.dtype != torch.int64 or edges.dim() != 1 or not edges.is_contiguous():
-            raise AmmsbError("link prediction: edges must be a contiguous 1-d int64 (uint64 bits) device tensor")
+        edges = _edge_keys(self.ctx, edges, "link prediction")
         out = self.ctx.empty((int(edges.numel()),), torch.float32)
         self.lp.check(self.lib.ammsb_linkpred_pairs(C.byref(pi.desc), _ptr(beta), float(epsilon), _ptr(edges),
                                                     int(edges.numel()), _ptr(out), _stream()))
@@ -954,11 +965,7 @@ class LinkCommunities:
         self.lib = _linkcomm.load()
 
     def _edges(self, edges):
-        if not torch.is_tensor(edges):
-            edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
-        if edges.dtype != torch.int64 or edges.dim() != 1 or not edges.is_contiguous():
-            raise AmmsbError("link communities: edges must be a contiguous 1-d int64 (uint64 bits) device tensor")
-        return edges
+        return _edge_keys(self.ctx, edges, "link communities")
 
     def _sizes(self, pi, sizes):
         if sizes is not None and (sizes.dtype != torch.int64 or sizes.numel() != pi.cols + 1
@@ -1024,10 +1031,7 @@ class CommunityQuality:
         (uint64 bits) device tensor.  -> counts [2K + 2] int64 on the device (internal[0..K), boundary[K..2K),
         uncovered, skipped), or (counts, shared [n] int32) with shared=True; counts=False leaves the counters out
         (-> None in their place)."""
-        if not torch.is_tensor(edges):
-            edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1))
-        if edges.dtype != torch.int64 or edges.dim() != 1 or not edges.is_contiguous():
-            raise AmmsbError("community quality: edges must be a contiguous 1-d int64 (uint64 bits) device tensor")
+        edges = _edge_keys(self.ctx, edges, "community quality")
         N, K, n = int(N), int(K), int(edges.numel())
         if mask.dtype != torch.int64 or not mask.is_contiguous() or \
                 not mask.numel() or mask.numel() * 8 != int(self.lib.ammsb_quality_mask_bytes(N, K)):
@@ -1075,12 +1079,9 @@ class CoverMatch:
         thr = self.cv.check_threshold(threshold)
         if not torch.is_tensor(offsets):
             offsets = self.ctx.from_numpy(np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1))
-        if not torch.is_tensor(members):
-            members = self.ctx.from_numpy(np.ascontiguousarray(members, dtype=np.uint32).reshape(-1))
         if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or offsets.numel() < 1:
             raise AmmsbError("cover match: offsets must be a contiguous 1-d int64 (uint64 bits) device tensor [G + 1]")
-        if members.dtype != torch.int32 or members.dim() != 1 or not members.is_contiguous():
-            raise AmmsbError("cover match: members must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        members = _u32_vector(self.ctx, members, "cover match: members")
         if detected_size.dtype != torch.int64 or detected_size.numel() != pi.cols or not detected_size.is_contiguous():
             raise AmmsbError("cover match: detected_size must be a contiguous [K] int64 device tensor")
         G, M, K = int(offsets.numel()) - 1, int(members.numel()), int(pi.cols)
@@ -1127,10 +1128,7 @@ class CoverNMI:
         """truth_size [G] (uint32 bits): a host array or a contiguous int32 device tensor; detected_size: the [K] int64
         device tensor CommunityReadout.sizes gives.  -> State: H_truth [G], H_detected [K] written, c_truth [G] and
         c_detected [K] at +inf."""
-        if not torch.is_tensor(truth_size):
-            truth_size = self.ctx.from_numpy(np.ascontiguousarray(truth_size, dtype=np.uint32).reshape(-1))
-        if truth_size.dtype != torch.int32 or truth_size.dim() != 1 or not truth_size.is_contiguous():
-            raise AmmsbError("cover NMI: truth_size must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        truth_size = _u32_vector(self.ctx, truth_size, "cover NMI: truth_size")
         if detected_size.dtype != torch.int64 or detected_size.dim() != 1 or not detected_size.is_contiguous():
             raise AmmsbError("cover NMI: detected_size must be a contiguous [K] int64 device tensor")
         G, K, c = int(truth_size.numel()), int(detected_size.numel()), self.ctx

@@ -59,10 +59,9 @@ def test_the_kernels_did_not_land_in_the_existing_library(cv):
     for form in cv.KERNEL_FORMS:   # as a kernel's (mangled) symbol and descriptor, not only as the dispatcher's string
         assert re.search(rb"_ZN[0-9A-Za-z_]*\d+" + form.encode() + rb"E[0-9A-Za-z_]*\.kd", raw), form
         assert form.encode() not in open(_capi.LIB_PATH, "rb").read(), form
-    csrc_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "Makefile")).read()
-    assert "libammsb_cover.so" in csrc_mk and "ammsb_cover.o" in csrc_mk
-    assert "CV_OUT" in re.search(r"^all:.*$", csrc_mk, re.M).group(0)
-    assert "ammsb_cover" not in re.search(r"^SRCS\s*=.*$", csrc_mk, re.M).group(0)   # not part of libammsb_hip.so
+    import make_dry_run as dry
+    assert dry.csrc_all_builds("../libammsb_cover.so", "ammsb_cover.o") and dry.csrc_all_builds("ammsb_cover.o", "-c ammsb_cover.hip")
+    assert "ammsb_cover" not in dry.hip_library_link()   # not part of libammsb_hip.so
     assert "*.so" in open(os.path.join(ROOT, ".gitignore")).read().split()
 
 
@@ -323,15 +322,19 @@ def test_command_line_refuses_the_bad_combinations():
     assert r.returncode == 2 and "Failed to detect file" in r.stderr
 
 
-def test_host_build_and_link_lines_carry_the_new_library():
-    host_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "host", "Makefile")).read()
-    links = [ln for ln in host_mk.splitlines() if "-lammsb_linkpred" in ln]
+def test_host_build_and_link_lines_carry_the_new_library(cv):
+    import make_dry_run as dry
+    links = dry.host_links()   # (every one of them carries every device library)
     assert len(links) >= 11 and all("-lammsb_quality" in ln and "-lammsb_cover" in ln for ln in links)
     asan = [ln for ln in links if "libammsb_host_asan.so" in ln or "-lrccl" in ln]
     assert len(asan) >= 4                                           # the host library twice, ammsb_main_asan, exchange_test_asan
-    assert "../libammsb_cover.so" in host_mk and "include/ammsb_cover.h" in host_mk
-    all_line = re.search(r"^all:.*$", host_mk, re.M).group(0)
-    assert "tests/cpp/cover_test.cc" in host_mk and "CV_TEST_OUT" in all_line and "CQ_TEST_OUT" in all_line
+    # the host library is linked again once libammsb_cover.so is newer, its objects compiled again once the header is
+    relinked = dry.commands("host", "../libammsb_host.so", remake_all=False, touched=("../libammsb_cover.so",))
+    assert dry.builds(relinked, "../libammsb_host.so") and not dry.builds(relinked, "learner.o")
+    recompiled = dry.commands("host", "../libammsb_host.so", remake_all=False, touched=("../../include/ammsb_cover.h",))
+    assert dry.builds(recompiled, "postfit.o", "-c postfit.cc") and dry.builds(recompiled, "learner.o", "-c learner.cc")
+    assert dry.host_all_builds("../cover_test", "tests/cpp/cover_test.cc")
+    assert dry.host_all_builds("../quality_test", "tests/cpp/quality_test.cc")
     assert os.path.exists(os.path.join(ROOT, "tests", "cpp", "cover_test.cc"))
     run_asan = open(os.path.join(ROOT, "tools", "run_asan.sh")).read()
     assert "tests/test_cover_host.py" in run_asan and "tests/test_quality_host.py" in run_asan

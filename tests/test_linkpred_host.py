@@ -58,9 +58,9 @@ def test_the_kernels_did_not_land_in_the_existing_library(lp):
     assert b"gfx950" in raw and b"linkpred_top_mfma_q128_v4" in raw and b"linkpred_tile" in raw
     src = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_linkpred.hip")).read()
     assert "__builtin_amdgcn_mfma_f32_32x32x2f32" in src
-    csrc_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "Makefile")).read()
-    assert "libammsb_linkpred.so" in csrc_mk and "ammsb_linkpred.o" in csrc_mk
-    assert "ammsb_linkpred" not in re.search(r"^SRCS\s*=.*$", csrc_mk, re.M).group(0)   # not part of libammsb_hip.so
+    import make_dry_run as dry
+    assert dry.csrc_all_builds("../libammsb_linkpred.so", "ammsb_linkpred.o") and dry.csrc_all_builds("ammsb_linkpred.o", "-c ammsb_linkpred.hip")
+    assert "ammsb_linkpred" not in dry.hip_library_link()   # not part of libammsb_hip.so
 
 
 def test_the_matrix_core_instruction_is_in_the_code_object(lp, tmp_path):
@@ -254,8 +254,8 @@ def test_command_line_refuses_the_bad_combinations(tmp_path):
 
 
 def test_build_and_link_lines_carry_the_new_library():
-    host_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "host", "Makefile")).read()
-    links = [ln for ln in host_mk.splitlines() if "-lammsb_refsample" in ln]
+    import make_dry_run as dry
+    links = [ln for ln in dry.commands("host", "all", "asan") if "-lammsb_refsample" in ln]
     assert links and all("-lammsb_linkpred" in ln for ln in links)     # the ASan variants included
     asan = open(os.path.join(ROOT, "tools", "run_asan.sh")).read()
     assert "tests/test_linkpred_host.py" in asan

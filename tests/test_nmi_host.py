@@ -59,9 +59,9 @@ def test_the_kernels_are_a_library_of_their_own(nm):
         assert b"ammsb_nmi" not in open(other, "rb").read()
     for form in nm.KERNEL_FORMS:   # as a kernel's (mangled) symbol and descriptor, not only as the dispatcher's string
         assert re.search(rb"_ZN[0-9A-Za-z_]*\d+" + form.encode() + rb"E[0-9A-Za-z_]*\.kd", raw), form
-    mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert "ammsb_nmi.o: ../../include/ammsb_nmi.h" in mk and "NM_OUT" in re.search(r"^all:.*$", mk, re.M).group(0)
-    assert "ammsb_nmi" not in re.search(r"^SRCS\s*=.*$", mk, re.M).group(0)   # not part of libammsb_hip.so
+    import make_dry_run as dry
+    assert dry.header_rebuilds_object("nmi") and dry.csrc_all_builds("../libammsb_nmi.so", "ammsb_nmi.o")
+    assert "ammsb_nmi" not in dry.hip_library_link()   # not part of libammsb_hip.so
     assert '#include "ammsb_postfit.h"' in open(os.path.join(PKG, "csrc", "ammsb_nmi.hip")).read()
 
 

@@ -64,12 +64,12 @@ def test_the_kernels_are_a_library_of_their_own(om):
     assert b"gfx950" in raw
     for form in om.KERNEL_FORMS:   # as a kernel's (mangled) symbol and descriptor, not only as the dispatcher's string
         assert re.search(rb"_ZN[0-9A-Za-z_]*\d+" + form.encode() + rb"E[0-9A-Za-z_]*\.kd", raw), form
-    mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
-    assert "ammsb_omega.o: ../../include/ammsb_omega.h" in mk and "OM_OUT" in re.search(r"^all:.*$", mk, re.M).group(0)
-    assert "ammsb_omega" not in re.search(r"^SRCS\s*=.*$", mk, re.M).group(0)   # not part of libammsb_hip.so
+    import make_dry_run as dry
+    assert dry.header_rebuilds_object("omega") and dry.csrc_all_builds("../libammsb_omega.so", "ammsb_omega.o")
+    assert "ammsb_omega" not in dry.hip_library_link()   # not part of libammsb_hip.so
     assert '#include "ammsb_postfit.h"' in open(os.path.join(PKG, "csrc", "ammsb_omega.hip")).read()
-    hmk = open(os.path.join(PKG, "host", "Makefile")).read()
-    assert re.search(r"^omega_test:", hmk, re.M) and "-lammsb_omega" in hmk and "OM_SCORE_OUT" in re.search(r"^all:.*$", hmk, re.M).group(0)
+    assert dry.builds(dry.commands("host", "omega_test"), "../omega_test", "tests/cpp/omega_test.cc", "-lammsb_omega")
+    assert dry.host_all_builds("../omega_score_test", "tests/cpp/omega_score_test.cc")
 
 
 def test_argument_errors_are_returned_before_anything_is_launched(om):

@@ -58,9 +58,9 @@ def test_the_kernels_did_not_land_in_the_existing_library(q):
     assert b"gfx950" in raw
     for form in q.KERNEL_FORMS:   # as a kernel's (mangled) symbol and descriptor, not only as the dispatcher's string
         assert re.search(rb"_ZN[0-9A-Za-z_]*\d+" + form.encode() + rb"E[0-9A-Za-z_]*\.kd", raw), form
-    csrc_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "Makefile")).read()
-    assert "libammsb_quality.so" in csrc_mk and "ammsb_quality.o" in csrc_mk
-    assert "ammsb_quality" not in re.search(r"^SRCS\s*=.*$", csrc_mk, re.M).group(0)   # not part of libammsb_hip.so
+    import make_dry_run as dry
+    assert dry.csrc_all_builds("../libammsb_quality.so", "ammsb_quality.o") and dry.csrc_all_builds("ammsb_quality.o", "-c ammsb_quality.hip")
+    assert "ammsb_quality" not in dry.hip_library_link()   # not part of libammsb_hip.so
 
 
 def _rpm(rows, cols, rows_in_block=0, blocks=1, ptr=0x1000):
@@ -222,11 +222,11 @@ def test_command_line_refuses_the_bad_combinations():
 
 
 def test_build_and_link_lines_carry_the_new_library():
-    host_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "host", "Makefile")).read()
-    links = [ln for ln in host_mk.splitlines() if "-lammsb_linkpred" in ln]
+    import make_dry_run as dry
+    links = dry.host_links()   # (every one of them carries every device library)
     assert len(links) >= 10 and all("-lammsb_linkcomm" in ln and "-lammsb_quality" in ln for ln in links)   # the ASan variants included
-    all_line = re.search(r"^all:.*$", host_mk, re.M).group(0)
-    assert "tests/cpp/quality_test.cc" in host_mk and "CQ_TEST_OUT" in all_line and "LC_TEST_OUT" in all_line
+    assert dry.host_all_builds("../quality_test", "tests/cpp/quality_test.cc")
+    assert dry.host_all_builds("../linkcomm_test", "tests/cpp/linkcomm_test.cc")
     asan = open(os.path.join(ROOT, "tools", "run_asan.sh")).read()
     assert "tests/test_quality_host.py" in asan and "tests/test_linkcomm_host.py" in asan
     ignored = open(os.path.join(ROOT, ".gitignore")).read().split()

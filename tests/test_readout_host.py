@@ -186,9 +186,8 @@ def test_no_cpu_path_without_a_gpu(ro, monkeypatch):
 
 
 def test_build_and_link_lines_carry_the_new_library():
-    host_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "host", "Makefile")).read()
-    links = [ln for ln in host_mk.splitlines() if "-lammsb_refsample" in ln]
+    import make_dry_run as dry
+    links = [ln for ln in dry.commands("host", "all", "asan") if "-lammsb_refsample" in ln]
     assert links and all("-lammsb_readout" in ln for ln in links)     # the ASan variants included
-    csrc_mk = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "Makefile")).read()
-    assert "libammsb_readout.so" in csrc_mk and "ammsb_readout.o" in csrc_mk
-    assert "ammsb_readout" not in re.search(r"^SRCS\s*=.*$", csrc_mk, re.M).group(0)   # not part of libammsb_hip.so
+    assert dry.csrc_all_builds("../libammsb_readout.so", "ammsb_readout.o") and dry.csrc_all_builds("ammsb_readout.o", "-c ammsb_readout.hip")
+    assert "ammsb_readout" not in dry.hip_library_link()   # not part of libammsb_hip.so
