@@ -163,6 +163,25 @@ class Learner {
   bool WriteCoverOmega(std::ostream* out, const std::vector<uint64_t>& offsets, const std::vector<uint32_t>& members,
                        Float threshold, const std::vector<uint32_t>& universe, uint64_t launch_pairs = 1ull << 31);
 
+  // How the detected communities relate to each other (include/ammsb_relate.h).  CommunityOverlap: overlap[K * K], the
+  // nodes a with pi[a, k] >= threshold and pi[a, l] >= threshold; symmetric, the diagonal holds the community sizes.  The
+  // nodes are cut into slabs of a multiple of 64 rows whose membership bits, K rows / 8 bytes, fit max_bytes (at least
+  // 64 rows); integer adds, so the result does not depend on max_bytes.  RelatedCommunities: per community the `top`
+  // (1..64) others that share at least max(1, min_overlap) nodes with it, ranked by `by` -- "overlap" (the shared nodes
+  // o), "jaccard" (o / (d_k + d_l - o)) or "contained" (o / d_l) -- as exact rationals, equal values by id ascending.
+  // std::invalid_argument on a bad threshold, measure or top.  Waits, reads and perturbs like CommunityQuality.
+  struct Related {
+    std::vector<uint64_t> size;     // [K]
+    std::vector<int32_t> partner;   // [K * top], -1 in an empty slot
+    std::vector<uint32_t> overlap;  // [K * top], the nodes shared with that partner, 0 in an empty slot
+  };
+  void CommunityOverlap(Float threshold, std::vector<uint32_t>* overlap, uint64_t max_bytes = 1ull << 30);
+  void RelatedCommunities(Float threshold, uint32_t top, const std::string& by, uint32_t min_overlap, Related* related,
+                          uint64_t max_bytes = 1ull << 30);
+  // `# N K threshold by top min_overlap`, then `k size n l0 o0 l1 o1 ...` per community: integers below the header.
+  bool WriteRelatedCommunities(std::ostream* out, Float threshold, uint32_t top, const std::string& by,
+                               uint32_t min_overlap = 1, uint64_t max_bytes = 1ull << 30);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

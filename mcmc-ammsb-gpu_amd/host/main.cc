@@ -77,9 +77,12 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy;
   bool haveCoverThreshold = false;
   double coverThreshold = 0.05;
+  bool haveRelatedThreshold = false, haveRelatedTop = false;
+  double relatedThreshold = 0.05;
+  long relatedTop = 4;
   bool haveQualityThreshold = false;
   double qualityThreshold = 0.05;
   bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
@@ -192,6 +195,22 @@ int main(int argc, char** argv) {
                in >> coverThreshold;
                return !in.fail() && in.eof();
              }},
+      OptStr("related-communities-out", 0, &relatedOut),  // (new) after the last perplexity line: `# N K threshold by top min_overlap`, then `k size n l0 o0 l1 o1 ...` per community: its n closest other communities and the nodes it shares with each
+      Option{"related-communities-threshold", 0, "0.05 (new, with --related-communities-out: a node is a member of k iff pi[a, k] >= it)",
+             [&](const std::string& v) {
+               haveRelatedThreshold = true;
+               std::istringstream in(v);
+               in >> relatedThreshold;
+               return !in.fail() && in.eof();
+             }},
+      Option{"related-communities-top", 0, "4 (new, with --related-communities-out: closest communities kept per community, 1..64)",
+             [&](const std::string& v) {
+               haveRelatedTop = true;
+               std::istringstream in(v);
+               in >> relatedTop;
+               return !in.fail() && in.eof();
+             }},
+      OptStr("related-communities-by", 0, &relatedBy),  // (new, with --related-communities-out) jaccard (default) | overlap | contained
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -285,6 +304,13 @@ int main(int argc, char** argv) {
     Fatal("--cover-omega-universe must be covered or all");
   if (!(coverThreshold >= 0) || !std::isfinite(static_cast<float>(coverThreshold)))
     Fatal("--cover-match-threshold must be finite and >= 0");
+  if ((haveRelatedThreshold || haveRelatedTop || !relatedBy.empty()) && relatedOut.empty())
+    Fatal("--related-communities-threshold / --related-communities-top / --related-communities-by need --related-communities-out FILE");
+  if (!relatedBy.empty() && relatedBy != "jaccard" && relatedBy != "overlap" && relatedBy != "contained")
+    Fatal("--related-communities-by must be jaccard, overlap or contained");
+  if (relatedTop < 1 || relatedTop > 64) Fatal("--related-communities-top must be in 1..64");
+  if (!(relatedThreshold >= 0) || !std::isfinite(static_cast<float>(relatedThreshold)))
+    Fatal("--related-communities-threshold must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -482,6 +508,20 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("cover Omega: ") + e.what());
+    }
+  }
+  if (!relatedOut.empty()) {
+    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(relatedOut);
+        if (!out.good() || !learner.WriteRelatedCommunities(&out, static_cast<mcmc::Float>(relatedThreshold),
+                                                            static_cast<uint32_t>(relatedTop),
+                                                            relatedBy.empty() ? "jaccard" : relatedBy))
+          Fatal("cannot write related communities " + relatedOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("related communities: ") + e.what());
     }
   }
   learner.PrintStats();

@@ -1,7 +1,7 @@
 // mcmc::Learner's post-fit analyses (include/mcmc/learner.h): what reads a fitted model out -- memberships and
-// communities, link prediction, link communities, community quality, and the three comparisons with a ground-truth cover
-// (F1 match, overlapping NMI, Omega index).  Each is a thin driver of one library of its own (libammsb_readout.so ...
-// libammsb_omega.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
+// communities, link prediction, link communities, community quality, the three comparisons with a ground-truth cover
+// (F1 match, overlapping NMI, Omega index), and how the detected communities relate to each other.  Each is a thin driver
+// of one library of its own (libammsb_readout.so ... libammsb_relate.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
 // read the results back, and for the Write* methods print them.  Nothing here touches the training loop of learner.cc.
 #include "mcmc/learner.h"
 #include "ammsb_readout.h"
@@ -11,6 +11,7 @@
 #include "ammsb_cover.h"
 #include "ammsb_nmi.h"
 #include "ammsb_omega.h"
+#include "ammsb_relate.h"
 
 #include <hip/hip_runtime.h>
 
@@ -682,5 +683,92 @@ bool Learner::WriteCoverOmega(std::ostream* out, const std::vector<uint64_t>& of
   return static_cast<bool>(*out);
 }
 
+
+// ---- how the detected communities relate to each other: libammsb_relate.so over slabs of pi
+namespace {
+uint32_t RelateMeasure(const std::string& by) {
+  if (by == "overlap") return AMMSB_RELATE_OVERLAP;
+  if (by == "jaccard") return AMMSB_RELATE_JACCARD;
+  if (by == "contained") return AMMSB_RELATE_CONTAINED;
+  throw std::invalid_argument("RelatedCommunities: the measure is \"overlap\", \"jaccard\" or \"contained\", not \"" + by + "\"");
+}
+
+// overlap[K, K] on the device, slab by slab; the stream is left running
+void OverlapOnDevice(const ammsb_rpm* pi, Float threshold, uint64_t max_bytes, clcuda::Buffer<uint32_t>* d_overlap,
+                     const clcuda::Context& context, void* stream) {
+  const uint64_t N = pi->num_rows, K = pi->num_cols;
+  if (K == 0 || K > AMMSB_RELATE_MAX_COLS) throw std::runtime_error("CommunityOverlap: K outside 1..8192");
+  hipError_t e = hipMemsetAsync((*d_overlap)(), 0, K * K * sizeof(uint32_t), static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) throw std::runtime_error(std::string("CommunityOverlap: memset: ") + hipGetErrorString(e));
+  if (N == 0) return;
+  const uint64_t step = std::min<uint64_t>((N + 63) / 64 * 64, std::max<uint64_t>(64, max_bytes * 8 / K / 64 * 64));
+  clcuda::Buffer<uint64_t> d_bits(context, K * (step / 64));
+  for (uint64_t lo = 0; lo < N; lo += step) {
+    const uint64_t n = std::min(step, N - lo);
+    int rc = ammsb_relate_bits(pi, threshold, lo, n, d_bits(), stream);
+    if (rc == AMMSB_OK) rc = ammsb_relate_pairs(d_bits(), static_cast<uint32_t>(K), n, (*d_overlap)(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_relate", rc, ammsb_relate_last_error());
+  }
+  // d_bits is freed on return: the slabs have to be through with it
+  e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) throw std::runtime_error(std::string("CommunityOverlap: ") + hipGetErrorString(e));
+}
+}  // namespace
+
+void Learner::CommunityOverlap(Float threshold, std::vector<uint32_t>* overlap, uint64_t max_bytes) {
+  CheckThreshold("CommunityOverlap", threshold);
+  if (max_bytes < 1) throw std::invalid_argument("CommunityOverlap: max_bytes must be at least 1");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t K = pi_->Cols();
+  clcuda::Buffer<uint32_t> d_overlap(queue_.GetContext(), K * K);
+  OverlapOnDevice(&pi_->Get(), threshold, max_bytes, &d_overlap, queue_.GetContext(), queue_.stream());
+  overlap->resize(K * K);
+  d_overlap.Read(queue_, K * K, overlap->data());
+  queue_.Finish();
+}
+
+void Learner::RelatedCommunities(Float threshold, uint32_t top, const std::string& by, uint32_t min_overlap,
+                                 Related* related, uint64_t max_bytes) {
+  CheckThreshold("RelatedCommunities", threshold);
+  const uint32_t measure = RelateMeasure(by);
+  if (top == 0 || top > AMMSB_RELATE_MAX_TOP) throw std::invalid_argument("RelatedCommunities: top must be in 1..64");
+  if (max_bytes < 1) throw std::invalid_argument("RelatedCommunities: max_bytes must be at least 1");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t K = pi_->Cols();
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint32_t> d_overlap(context, K * K), d_shared(context, K * top);
+  clcuda::Buffer<int32_t> d_partner(context, K * top);
+  OverlapOnDevice(&pi_->Get(), threshold, max_bytes, &d_overlap, context, queue_.stream());
+  const int rc = ammsb_relate_top(d_overlap(), static_cast<uint32_t>(K), measure, top, min_overlap, d_partner(), d_shared(),
+                                  queue_.stream());
+  if (rc != AMMSB_OK) throw PostfitError("ammsb_relate_top", rc, ammsb_relate_last_error());
+  related->partner.resize(K * top);
+  related->overlap.resize(K * top);
+  d_partner.Read(queue_, K * top, related->partner.data());
+  d_shared.Read(queue_, K * top, related->overlap.data());
+  std::vector<uint32_t> matrix(K * K);
+  d_overlap.Read(queue_, K * K, matrix.data());
+  queue_.Finish();
+  related->size.resize(K);
+  for (uint64_t k = 0; k < K; ++k) related->size[k] = matrix[k * K + k];
+}
+
+bool Learner::WriteRelatedCommunities(std::ostream* out, Float threshold, uint32_t top, const std::string& by,
+                                      uint32_t min_overlap, uint64_t max_bytes) {
+  Related r;
+  RelatedCommunities(threshold, top, by, min_overlap, &r, max_bytes);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << G9(threshold) << " " << by << " " << top << " " << min_overlap
+       << "\n";
+  for (size_t k = 0; k < r.size.size(); ++k) {
+    uint32_t n = 0;
+    while (n < top && r.partner[k * top + n] >= 0) ++n;
+    *out << k << " " << r.size[k] << " " << n;
+    for (uint32_t t = 0; t < n; ++t) *out << " " << r.partner[k * top + t] << " " << r.overlap[k * top + t];
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
 
 }  // namespace mcmc

@@ -1207,6 +1207,60 @@ class CoverOmega:
         return self.om.last_kernel_name()
 
 
+class CommunityRelations:
+    """How the detected communities relate to each other (include/ammsb_relate.h): community-major membership bits from
+    one streaming pass over a slab of pi, the K x K matrix of shared nodes by AND + population count over those bits,
+    and per community the partners it overlaps most.  Integer counts over binary32 compares and integer compares of
+    rationals: exact, and independent of how the nodes are cut into slabs.  Owns nothing but the tensors it returns."""
+
+    def __init__(self, ctx):
+        from . import _relate
+        self.ctx = ctx
+        self.rl = _relate
+        self.lib = _relate.load()
+
+    def bits(self, pi, thr, rows=None):
+        """rows: (lo, hi) with lo a multiple of 64, default all of pi -> the bits of rows lo .. hi - 1: a [K, ceil((hi -
+        lo) / 64)] int64 device tensor, bit (a - lo) & 63 of word (a - lo) >> 6 of row k set iff pi[a, k] >= thr"""
+        thr = self.rl.check_threshold(thr)
+        lo, hi = (0, int(pi.desc.num_rows)) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= lo <= hi:
+            raise AmmsbError("community relations: rows (%d, %d) is not a range" % (lo, hi))
+        K, n = int(pi.cols), hi - lo
+        out = self.ctx.empty((K, (n + 63) // 64), torch.int64)
+        if n:  # (an empty tensor has no address)
+            self.rl.check(self.lib.ammsb_relate_bits(C.byref(pi.desc), thr, lo, n, _ptr(out), _stream()))
+        return out
+
+    def pairs(self, bits, K, rows, overlap):
+        """adds the shared nodes of one slab -- bits as bits() gives them for `rows` rows -- to overlap, a [K, K] int32
+        (uint32 bits) device tensor that the caller zeroed before the first slab"""
+        K, rows = int(K), int(rows)
+        if bits.dtype != torch.int64 or not bits.is_contiguous() or bits.numel() != K * ((rows + 63) // 64):
+            raise AmmsbError("community relations: not the bits of %d rows and %d communities" % (rows, K))
+        if overlap.dtype != torch.int32 or not overlap.is_contiguous() or tuple(overlap.shape) != (K, K):
+            raise AmmsbError("community relations: overlap must be a contiguous [K, K] int32 (uint32 bits) device tensor")
+        if rows:
+            self.rl.check(self.lib.ammsb_relate_pairs(_ptr(bits), K, rows, _ptr(overlap), _stream()))
+
+    def top(self, overlap, by="jaccard", top=4, min_overlap=1):
+        """overlap: the finished [K, K] int32 (uint32 bits) device tensor -> (partner [K, top] int32, shared [K, top]
+        int32 (uint32 bits)) on the device: per community the `top` others that share at least max(1, min_overlap) nodes
+        with it, ranked by `by` (overlap, jaccard or contained), equal values by id ascending; -1 and 0 in empty slots"""
+        measure, top, min_overlap = self.rl.check_args(by, top, min_overlap)
+        if overlap.dtype != torch.int32 or not overlap.is_contiguous() or overlap.dim() != 2 or \
+                overlap.shape[0] != overlap.shape[1] or not overlap.numel():
+            raise AmmsbError("community relations: overlap must be a contiguous [K, K] int32 (uint32 bits) device tensor")
+        K = int(overlap.shape[0])
+        partner, shared = self.ctx.empty((K, top), torch.int32), self.ctx.empty((K, top), torch.int32)
+        self.rl.check(self.lib.ammsb_relate_top(_ptr(overlap), K, measure, top, min_overlap, _ptr(partner), _ptr(shared),
+                                                _stream()))
+        return partner, shared
+
+    def kernel_name(self):
+        return self.rl.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

@@ -1,6 +1,6 @@
 """The post-fit analyses of a Learner: what reads a fitted model out -- memberships and communities, link prediction,
-link communities, community quality, and the three comparisons with a ground-truth cover (F1 match, overlapping NMI,
-Omega index).  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
+link communities, community quality, the three comparisons with a ground-truth cover (F1 match, overlapping NMI, Omega
+index), and how the detected communities relate to each other.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
 holds all of pi, so none is a collective), and nothing of the iteration is touched -- no RNG stream, no counter, no
 buffer.  There is no CPU path: without a device every one of them raises."""
 import numpy as np
@@ -322,3 +322,42 @@ class PostFit:
         if int(h[3 * L]):
             raise AmmsbError("cover omega: %d pairs at or past level %d, which no node reaches" % (int(h[3 * L]), L))
         return _omega.Omega(threshold, n, h[:L], h[L:2 * L], h[2 * L:3 * L], int(tally[0]), int(tally[1]), K, G)
+
+    # ---- how the detected communities relate to each other (include/ammsb_relate.h)
+    def _relate(self):
+        return self._postfit_op("_community_relations", "CommunityRelations", "the community relations")
+
+    def CommunityOverlap(self, threshold=0.05, max_bytes=1 << 30):
+        """-> [K, K] int32 device tensor that holds uint32 bits (view it as uint32 on the host): overlap[k, l] = the nodes
+        a with pi[a, k] >= threshold and pi[a, l] >= threshold; symmetric, the diagonal is CommunitySizes(threshold).  The
+        nodes are cut into slabs of a multiple of 64 rows whose membership bits, K rows / 8 bytes, fit max_bytes (at
+        least 64 rows).  Integer adds: exact, and the result does not depend on max_bytes."""
+        from . import _relate
+        threshold = _relate.check_threshold(threshold)
+        if int(max_bytes) < 1:
+            raise AmmsbError("community relations: max_bytes must be at least 1")
+        N, K = self.cfg.N, self.cfg.K
+        step = _relate.slab_rows(K, max_bytes)
+        cr = self._relate()
+        self.drain()
+        overlap = self.ctx.zeros((K, K), torch.int32)
+        for lo in range(0, N, step):
+            hi = min(lo + step, N)
+            cr.pairs(cr.bits(self.pi, threshold, rows=(lo, hi)), K, hi - lo, overlap)
+        return overlap
+
+    def RelatedCommunities(self, threshold=0.05, top=4, by="jaccard", min_overlap=1, max_bytes=1 << 30, dense=False):
+        """-> _relate.Related: per community k the `top` other communities l that share at least max(1, min_overlap)
+        nodes with it, ranked by `by` -- "overlap" (the shared nodes o), "jaccard" (o / (d_k + d_l - o)) or "contained"
+        (o / d_l, the share of l inside k) -- as exact rationals, equal values by id ascending: .size, .partner (-1 in
+        an empty slot), .overlap, and in float64 on the host .jaccard, .inside and .contained; .matrix (the whole
+        CommunityOverlap, on the host) with dense=True; .duplicates() and .nested() list the pairs that reach a bound.
+        The integers are exact and do not depend on max_bytes."""
+        from . import _relate
+        threshold = _relate.check_threshold(threshold)
+        _, top, min_overlap = _relate.check_args(by, top, min_overlap)
+        overlap = self.CommunityOverlap(threshold, max_bytes)
+        partner, shared = self._relate().top(overlap, by, top, min_overlap)
+        matrix = overlap.cpu().numpy().view(np.uint32)
+        return _relate.Related(threshold, by, min_overlap, np.diagonal(matrix).astype(np.int64), partner.cpu().numpy(),
+                               shared.cpu().numpy().view(np.uint32), matrix if dense else None, N=self.cfg.N)
