@@ -14,18 +14,12 @@ import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
-from quality_child import ABOVE, BELOW, PLANTED, Raw, draw_rows, planted_cols  # noqa: E402  (the rows of the sibling group)
+from quality_child import ABOVE, BELOW, PLANTED, draw_rows, planted_cols  # noqa: F401  (the rows of the sibling group)
 
 NONE = 0xFFFFFFFF
-GUARD = 64                      # words past every output and past the workspace that must stay untouched
 FILL32, FILL64 = 0x5A5A5A5A, 0x5A5A5A5A5A5A
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 SEEN = set()
 F32 = np.float32
 UNIT = 128
@@ -114,39 +108,15 @@ def special_sizes(G, rng):
     return head + rng.integers(0, 40, G - len(head)).tolist()
 
 
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import _cover, ops
-        self.torch, self.ops, self.cv = torch, ops, _cover
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
+        from mcmc_ammsb_gpu_amd import _cover
+        super().__init__()
+        self.cv = _cover
         self.lib = _cover.load()
-        self.api = ops.CoverMatch(self.ctx)
-        self.ro = ops.CommunityReadout(self.ctx)
+        self.api = self.ops.CoverMatch(self.ctx)
+        self.ro = self.ops.CommunityReadout(self.ctx)
         assert _cover.UNIT == UNIT
-
-    def matrix(self, host, rows_in_block=0):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], rows_in_block)
-        pi.load(host)
-        return pi
-
-    def misaligned(self, host):
-        """one block whose base is 4 bytes past a 16-byte boundary"""
-        from mcmc_ammsb_gpu_amd._capi import Rpm
-        buf = self.ctx.empty((host.size + 1,), self.torch.float32)
-        buf[1:].copy_(self.ctx.from_numpy(host.reshape(-1)))
-        d = Rpm()
-        d.blocks[0] = buf.data_ptr() + 4
-        assert d.blocks[0] % 16 == 4
-        d.rows_in_block, d.num_rows, d.num_cols, d.num_blocks = host.shape[0], host.shape[0], host.shape[1], 1
-        r = Raw(d, host.shape[1], buf)
-        r.rows = host.shape[0]
-        return r
-
-    def guarded(self, words, dtype, fill):
-        buf = self.ctx.empty((words + GUARD,), dtype)
-        buf.fill_(fill)
-        return buf
 
     def match(self, pi, thr, offsets, members, dense=True, dsize=None):
         """the library call over buffers of this test's own, each followed by GUARD words that must survive
@@ -358,7 +328,7 @@ def forms_group():
         ref = reference(host, 0.05, off, mem)
         check(got, ref, "forms K=%d" % K)
         assert ref["truth_overlap"][1] > 0 and ref["truth_overlap"][3] > 0      # the crossing communities matched
-    src = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_cover.hip")).read()
+    src = open(os.path.join(ps.ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_cover.hip")).read()
     in_source = set(re.findall(r'"(cover_[a-z0-9_]+)"', src))
     assert in_source == set(b.cv.KERNEL_FORMS), in_source ^ set(b.cv.KERNEL_FORMS)
     print("forms seen: %s" % " ".join(sorted(SEEN)), flush=True)
@@ -435,23 +405,16 @@ def constructed_group():
 
 
 def learner_group(graph):
-    from linkpred_child import _pi_beta_of_checkpoint, _same_buffers
-    from readout_child import _sample_buffers
     from mcmc_ammsb_gpu_amd import _cover, hostlib
     from mcmc_ammsb_gpu_amd._capi import AmmsbError
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     off, mem = hostlib.generate_cover(N, k_true, seed=20260101)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
     lrn = make()
     lrn.Run(30)
     ck = io.BytesIO()
     lrn.Serialize(ck)
-    host, _ = _pi_beta_of_checkpoint(ck.getvalue(), N, K)
+    host, _ = ps.pi_beta_of_checkpoint(ck.getvalue(), N, K)
     assert np.array_equal(host.view(np.uint32), lrn.pi.host().view(np.uint32))
     lists = [mem[int(off[g]):int(off[g + 1])].tolist() for g in range(k_true)]
     for thr in (0.05, 0.01, 0.0, 2.0):
@@ -479,41 +442,25 @@ def learner_group(graph):
         r = lrn.CompareCover(none, 0.05)
         assert (r.detected_best == -1).all() and (r.truth_best == -1).all() and r.f1_truth == -1.0 and r.avg_f1 == -1.0
         assert np.array_equal(r.detected_size, lrn.CommunitySizes(0.05).cpu().numpy())
-    for bad in (lambda: lrn.CompareCover(lists, -1.0), lambda: lrn.CompareCover(lists, float("nan")),
-                lambda: lrn.CompareCover((np.array([0, 9]), mem[:3]))):
-        try:
-            bad()
-        except AmmsbError:
-            pass
-        else:
-            raise AssertionError("a bad argument was accepted")
+    ps.rejects(AmmsbError, (lambda: lrn.CompareCover(lists, -1.0), lambda: lrn.CompareCover(lists, float("nan")),
+                            lambda: lrn.CompareCover((np.array([0, 9]), mem[:3]))))
     lrn.close()
     # Run(20), the calls, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.CompareCover((off, mem))
-    a.CompareCover(lists, 0.01, dense=True)
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + cover match + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.CompareCover((off, mem))
+        a.CompareCover(lists, 0.01, dense=True)
+    ps.unperturbed_run(make, calls, "cover match")
     print("learner ok graph=%s" % graph, flush=True)
 
 
 def _check_match_file(path, ckpt, K, thr, offsets, members, what):
     """a cover-match file against the statement over the pi of the checkpoint the same process wrote; the Python writer
     reproduces its bytes"""
-    from linkpred_child import _pi_beta_of_checkpoint
     from mcmc_ammsb_gpu_amd import _cover
     fN, m, _ = _cover.read_cover_match(path)
     assert m.detected_best.size == K and F32(m.threshold) == F32(thr), (m.detected_best.size, m.threshold)
-    pi, _ = _pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
+    pi, _ = ps.pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
     ref = reference(pi, F32(thr), offsets, members)
     got = {n: getattr(m, n) for n in NAMES}
     got["skipped"] = m.skipped
@@ -528,14 +475,10 @@ def _check_match_file(path, ckpt, K, thr, offsets, members, what):
 
 
 def cpp_group():
-    import subprocess
     import tempfile
     from mcmc_ammsb_gpu_amd import _cover, hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "cover_test"), d], capture_output=True, text=True, timeout=240)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("cover_test", d, 240)
         lists = [[int(w) for w in ln.split()[1:]] for ln in open(os.path.join(d, "truth.txt"))]
         offsets, members = _cover.check_cover(lists)
         fN, m = _check_match_file(os.path.join(d, "match.txt"), os.path.join(d, "cpp.ckpt"), 64, 0.05, offsets, members,
@@ -553,9 +496,7 @@ def cpp_group():
         tail = ["-k", "48", "-m", "256", "-n", "16", "-x", "60", "-i", "30", "--ground-truth", truth, "--cover-match-out", out,
                 "--checkpoint-out", ck]
         for extra, thr in (([], 0.05), (["--cover-match-threshold", "0.01"], 0.01)):
-            r = subprocess.run([os.path.join(pkg, "ammsb_main"), "--load-data", "1", "--load-file", f] + tail + extra,
-                               capture_output=True, text=True, timeout=240)
-            assert r.returncode == 0, r.stderr[-3000:]
+            r = ps.run_ammsb_main(["--load-data", "1", "--load-file", f] + tail + extra, 240)
             assert "8 communities, %d members, 0 ids the graph never mentions dropped" % tmem.size in r.stderr
             fN, m = _check_match_file(out, ck, 48, thr, toff, tmem, "ammsb_main dump thr=%g" % thr)
             assert fN == N and m.truth_best.size == 8 and m.skipped == 0
@@ -576,38 +517,24 @@ def cpp_group():
                 fh.write(" ".join("%d" % a for a in mem + [3, 5][:g % 3]) + "\n")     # (3 and 5 are nobody's id)
         woff, wmem, dropped = _cover.read_cover(truth, dense_of)
         assert dropped > 0 and woff.size == 9
-        r = subprocess.run([os.path.join(pkg, "ammsb_main"), "-f", txt] + tail, capture_output=True, text=True, timeout=240)
-        assert r.returncode == 0, r.stderr[-3000:]
+        r = ps.run_ammsb_main(["-f", txt] + tail, 240)
         assert "8 communities, %d members, %d ids the graph never mentions dropped" % (wmem.size, dropped) in r.stderr
         gN, m = _check_match_file(out, ck, 48, 0.05, woff, wmem, "ammsb_main text graph")
         assert gN == fN and m.truth_best.size == 8 and m.skipped == 0 and int(m.truth_size.sum()) == wmem.size
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "exact":
-        exact_group(tuple(int(k) for k in argv[1:]) or (1, 3, 64, 65, 100, 256, 260, 1024, 2048, 8192))
-    elif kind == "persistent":
-        persistent_group(tuple(int(k) for k in argv[1:]) or (64, 256, 1024, 8192))
-    elif kind == "layout":
-        layout_group()
-    elif kind == "forms":
-        forms_group()
-    elif kind == "big":
-        big_group()
-    elif kind == "constructed":
-        constructed_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "exact": lambda a: exact_group(tuple(int(k) for k in a) or (1, 3, 64, 65, 100, 256, 260, 1024, 2048, 8192)),
+    "persistent": lambda a: persistent_group(tuple(int(k) for k in a) or (64, 256, 1024, 8192)),
+    "layout": lambda a: layout_group(),
+    "forms": lambda a: forms_group(),
+    "big": lambda a: big_group(),
+    "constructed": lambda a: constructed_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

@@ -8,22 +8,15 @@
         derives (at most K + 3 roundings touch a summand), not a measured one.
   (iii) sizes against np.bincount of the reference's slot 0, the edges with valid ends and no slot counted at K."""
 import ctypes as C
-import io
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
 NONE = 0xFFFFFFFF
 EPS = float(np.float32(1e-7))
-GUARD = 64                      # words past every output that must stay untouched
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 SEEN = set()
 F32 = np.float32
 
@@ -118,58 +111,24 @@ def reference(pi, beta, eps, edges, T, min_term):
     return ids, terms, p64, bound, valid, slot0
 
 
-class Raw:
-    """a descriptor that is not a RowPartitionedMatrix: what the library call needs of one"""
-
-    def __init__(self, desc, cols, keep):
-        self.desc, self.cols, self.keep = desc, cols, keep
-
-
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import _linkcomm, ops
-        self.torch, self.ops, self.lc = torch, ops, _linkcomm
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
+        from mcmc_ammsb_gpu_amd import _linkcomm
+        super().__init__()
+        self.lc = _linkcomm
         self.lib = _linkcomm.load()
-        self.api = ops.LinkCommunities(self.ctx)
-
-    def matrix(self, host, rows_in_block=0):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], rows_in_block)
-        pi.load(host)
-        return pi
-
-    def misaligned(self, host):
-        """one block whose base is 4 bytes past a 16-byte boundary"""
-        from mcmc_ammsb_gpu_amd._capi import Rpm
-        buf = self.ctx.empty((host.size + 1,), self.torch.float32)
-        buf[1:].copy_(self.ctx.from_numpy(host.reshape(-1)))
-        d = Rpm()
-        d.blocks[0] = buf.data_ptr() + 4
-        assert d.blocks[0] % 16 == 4
-        d.rows_in_block, d.num_rows, d.num_cols, d.num_blocks = host.shape[0], host.shape[0], host.shape[1], 1
-        return Raw(d, host.shape[1], buf)
-
-    def dev(self, a):
-        return self.ctx.from_numpy(a)
+        self.api = self.ops.LinkCommunities(self.ctx)
 
     def call(self, pi, beta, edges, T, min_term=0.0, eps=EPS, tops=True, prob=True, sizes=True):
         """the library call over outputs of this test's own, each followed by GUARD words of a pattern that must
         survive -> (ids, terms, prob, sizes) as numpy arrays (None for the outputs not asked for)"""
-        t, c = self.torch, self.ctx
+        t, guarded = self.torch, self.guarded
         n, K = int(edges.size), pi.cols
         d_edges = self.dev(np.ascontiguousarray(edges, dtype=np.uint64))
-
-        def guarded(words, dtype, fill):
-            buf = c.empty((words + GUARD,), dtype)
-            buf.fill_(fill)
-            return buf
         ids = guarded(n * T, t.int32, 0x5A5A5A5A) if tops else None
         terms = guarded(n * T, t.float32, 7.25) if tops else None
         pr = guarded(n, t.float32, 7.25) if prob else None
-        sz = guarded(K + 1, t.int64, 0x5A5A5A5A5A5A) if sizes else None
-        if sz is not None:
-            sz[:K + 1] = 0
+        sz = guarded(K + 1, t.int64, 0x5A5A5A5A5A5A, zero=True) if sizes else None
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None   # noqa: E731
         self.lc.check(self.lib.ammsb_linkcomm_edges(C.byref(pi.desc), ptr(beta), eps, ptr(d_edges), n, T, min_term,
                                                     ptr(ids), ptr(terms), ptr(pr), ptr(sz), None))
@@ -346,7 +305,7 @@ def forms_group():
         got = b.call(b.matrix(host), b.dev(beta_h), edges, 4)
         assert b.lc.last_kernel_name() == "linkcomm_" + form, (K, b.lc.last_kernel_name())
         check(got, reference(host, beta_h, EPS, edges, 4, 0.0), K, "forms K=%d" % K)
-    src = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_linkcomm.hip")).read()
+    src = open(os.path.join(ps.ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_linkcomm.hip")).read()
     in_source = set(re.findall(r'"(linkcomm_(?:fast|generic)[a-z0-9_]*)"', src))
     assert in_source == set(_linkcomm.KERNEL_FORMS), in_source ^ set(_linkcomm.KERNEL_FORMS)
     print("forms seen: %s" % " ".join(sorted(SEEN)), flush=True)
@@ -383,17 +342,9 @@ def big_group():
 
 
 def learner_group(graph):
-    from linkpred_child import _same_buffers
-    from readout_child import _sample_buffers
-    from mcmc_ammsb_gpu_amd import hostlib
     from mcmc_ammsb_gpu_amd._capi import AmmsbError
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     lrn = make()
     lrn.Run(30)
     host, beta_h, eps = lrn.pi.host(), lrn.beta.cpu().numpy(), lrn.params.epsilon
@@ -436,14 +387,8 @@ def learner_group(graph):
     out = tuple(t.cpu().numpy() for t in lrn.LinkCommunities(np.array([(N << 32) | 3, some[0]], dtype=np.uint64), top=2))
     assert (out[0][0] == -1).all() and (out[1][0].view(np.uint32) == 0).all() and out[2][0] == -1.0
     assert np.array_equal(out[0][1], one[0][0, :2]) and np.array_equal(out[1][1].view(np.uint32), one[1][0, :2].view(np.uint32))
-    for bad in (lambda: lrn.LinkCommunities(top=0), lambda: lrn.LinkCommunities(top=17),
-                lambda: lrn.LinkCommunities(min_term=-1.0), lambda: lrn.LinkCommunitySizes(float("nan"))):
-        try:
-            bad()
-        except AmmsbError:
-            pass
-        else:
-            raise AssertionError("a bad argument was accepted")
+    ps.rejects(AmmsbError, (lambda: lrn.LinkCommunities(top=0), lambda: lrn.LinkCommunities(top=17),
+                            lambda: lrn.LinkCommunities(min_term=-1.0), lambda: lrn.LinkCommunitySizes(float("nan"))))
     # slabs: a budget that cuts the links into many calls gives the same tensors
     whole = tuple(t.cpu().numpy() for t in lrn.LinkCommunities(top=4))
     lrn.LINKCOMM_SLAB_BYTES = 36 * 1000
@@ -451,34 +396,24 @@ def learner_group(graph):
     assert all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(whole, cut))
     lrn.close()
     # Run(20), the calls, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.TrainingLinks()
-    a.LinkCommunities(top=4)
-    a.LinkCommunitySizes(1e-3)
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + link communities + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.TrainingLinks()
+        a.LinkCommunities(top=4)
+        a.LinkCommunitySizes(1e-3)
+    ps.unperturbed_run(make, calls, "link communities")
     print("learner ok graph=%s" % graph, flush=True)
 
 
 def _check_file(path, ckpt, K, top, min_term):
     """a link-communities file against the numpy statement over the pi and beta of the checkpoint the same process
     wrote; the Python writer reproduces its bytes"""
-    from linkpred_child import _pi_beta_of_checkpoint
     from mcmc_ammsb_gpu_amd import _linkcomm
     fN, fK, ftop, fmin, edges, prob, ids, terms = _linkcomm.read_link_communities(path)
     assert (fK, ftop, F32(fmin)) == (K, top, F32(min_term)), (fK, ftop, fmin)
     u, v = edges >> np.uint64(32), edges & np.uint64(NONE)
     assert (u < v).all() and (v < fN).all() and (np.diff(edges.astype(np.int64)) > 0).all()
-    pi, beta = _pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
+    pi, beta = ps.pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
     check((ids, terms, prob, None), reference(pi, beta, EPS, edges, top, F32(min_term)), K, os.path.basename(path))
     again = path + ".py"
     _linkcomm.write_link_communities(again, fN, fK, ftop, fmin, edges, prob, ids.view(np.int32), terms)
@@ -487,14 +422,10 @@ def _check_file(path, ckpt, K, top, min_term):
 
 
 def cpp_group():
-    import subprocess
     import tempfile
     from mcmc_ammsb_gpu_amd import hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "linkcomm_test"), d], capture_output=True, text=True, timeout=240)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("linkcomm_test", d, 240)
         fN, E = _check_file(os.path.join(d, "linkcomm.txt"), os.path.join(d, "cpp.ckpt"), 64, 3, 0.0)
         assert fN == 20000 and E > 100000
         print("cpp ok: Learner::WriteLinkCommunities equals the statement over the checkpoint's pi", flush=True)
@@ -503,39 +434,26 @@ def cpp_group():
         f = os.path.join(d, "g.bin.gz")
         hostlib.dump_dataset(f, N, 0.02, hostlib.generate_graph(N, 8, 12, seed=3))
         out, ck = os.path.join(d, "lc.txt"), os.path.join(d, "main.ckpt")
-        base = [os.path.join(pkg, "ammsb_main"), "--load-data", "1", "--load-file", f, "-k", "48", "-m", "256", "-n", "16",
-                "-x", "60", "-i", "30", "--link-communities-out", out, "--checkpoint-out", ck]
+        base = ["--load-data", "1", "--load-file", f, "-k", "48", "-m", "256", "-n", "16", "-x", "60", "-i", "30",
+                "--link-communities-out", out, "--checkpoint-out", ck]
         for extra, top, min_term in (([], 1, 0.0),
                                      (["--link-communities-top", "16", "--link-communities-min-term", "0.001"], 16, 0.001)):
-            r = subprocess.run(base + extra, capture_output=True, text=True, timeout=240)
-            assert r.returncode == 0, r.stderr[-3000:]
+            ps.run_ammsb_main(base + extra, 240)
             fN, E = _check_file(out, ck, 48, top, min_term)
             assert fN == N and E > 1000
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "exact":
-        exact_group(tuple(int(k) for k in argv[1:]) or (1, 3, 64, 100, 256, 260, 512, 1024, 2048, 8192))
-    elif kind == "persistent":
-        persistent_group(tuple(int(k) for k in argv[1:]) or (256, 1024, 1280, 2048))
-    elif kind == "layout":
-        layout_group()
-    elif kind == "forms":
-        forms_group()
-    elif kind == "big":
-        big_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "exact": lambda a: exact_group(tuple(int(k) for k in a) or (1, 3, 64, 100, 256, 260, 512, 1024, 2048, 8192)),
+    "persistent": lambda a: persistent_group(tuple(int(k) for k in a) or (256, 1024, 1280, 2048)),
+    "layout": lambda a: layout_group(),
+    "forms": lambda a: forms_group(),
+    "big": lambda a: big_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

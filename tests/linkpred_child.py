@@ -7,24 +7,18 @@ Learner.LinkProbabilities / PredictLinks / HeldoutAUC) against numpy statements.
        constant covers products that underflow binary32), not measured.
   (ii) top against np.argsort(-row, kind="stable") over block's row with the ineligible entries removed: ids as
        integers, scores by bit pattern.  No tolerance."""
-import io
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
 NONE = 0xFFFFFFFF
 KS = (1, 3, 48, 64, 113, 256, 512, 1024, 2048, 4096, 8192)
 QS = (1, 31, 32, 33, 200)
 CANDS = (1, 63, 65, 5000)
 EPS = float(np.float32(1e-7))
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 SEEN = set()
 
 
@@ -76,21 +70,10 @@ def p64_pairs(pi, beta, eps, u, v):
     return p, (pi.shape[1] + 8) * 2.0 ** -24 * M + 2.0 ** -100
 
 
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import ops
-        self.torch, self.ops = torch, ops
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
-        self.lp = ops.LinkPredictor(self.ctx)
-
-    def matrix(self, host, rows_in_block=0):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], rows_in_block)
-        pi.load(host)
-        return pi
-
-    def dev(self, a):
-        return self.ctx.from_numpy(a)
+        super().__init__()
+        self.lp = self.ops.LinkPredictor(self.ctx)
 
     def block(self, pi, beta, q, cand, eps=EPS):
         out = self.lp.block(pi, beta, eps, np.asarray(q, dtype=np.uint32), cand)
@@ -303,7 +286,7 @@ def forms_group():
     import re
     accuracy_group(ks=(48, 113), qs=(1, 200), cands=(65,))
     selection_group(ks=(48, 113), qs=(1, 200), ts=(10,))
-    src = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_linkpred.hip")).read()
+    src = open(os.path.join(ps.ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_linkpred.hip")).read()
     in_source = set(re.findall(r'"(linkpred_(?:block|top|pairs)_[a-z0-9_]+)"', src))
     assert in_source == set(_linkpred.KERNEL_FORMS), in_source ^ set(_linkpred.KERNEL_FORMS)
     print("forms seen: %s" % " ".join(sorted(SEEN)), flush=True)
@@ -432,36 +415,11 @@ def planted_group():
     print("planted ok", flush=True)
 
 
-def _same_buffers(a, b, what, partly):
-    """Every buffer record byte for byte, as the read-out test compares them (readout_child._same_buffers): the
-    per-sample device buffers over the bytes the pending mini-batch holds.  The short records carry accumulated wall
-    times as varints, whose LENGTH changes when a time crosses a power of 128 ns, so they are counted, not measured."""
-    from readout_child import _records
-    ra, rb = _records(a), _records(b)
-    assert len(ra) == len(rb) and sum(len(x) >= 200 for x in ra) >= 6, what
-    cut = {}
-    for i, total, valid in partly:
-        head = len(ra[i]) - total
-        assert 2 <= head <= 11 and valid <= total, (what, i, len(ra[i]), total)
-        cut[i] = head + valid
-    for i, (x, y) in enumerate(zip(ra, rb)):
-        assert (len(x) >= 200) == (len(y) >= 200), (what, i)
-        if len(x) >= 200:
-            n = cut.get(i, len(x))
-            assert len(x) == len(y) and x[:n] == y[:n], "%s: record %d (%d bytes) differs" % (what, i, len(x))
-
-
 def learner_group(graph):
-    from readout_child import _sample_buffers
-    from mcmc_ammsb_gpu_amd import _linkpred, hostlib
+    from mcmc_ammsb_gpu_amd import _linkpred
     from mcmc_ammsb_gpu_amd._capi import AmmsbError
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     lrn = make()
     lrn.Run(30)
     host, beta_h, eps = lrn.pi.host(), lrn.beta.cpu().numpy(), lrn.params.epsilon
@@ -508,14 +466,8 @@ def learner_group(graph):
     print("held-out links among the top 10 with exclude=('training',): %d" % int(hit.sum()), flush=True)
     same_top(tuple(t.cpu().numpy().view(np.uint32) if j == 0 else t.cpu().numpy() for j, t in
                    enumerate(lrn.PredictLinks(nodes, top=10, exclude=()))), want(np.zeros_like(in_t)), "PredictLinks, exclude nothing")
-    for bad in (lambda: lrn.PredictLinks(nodes, top=0), lambda: lrn.PredictLinks(nodes, top=65),
-                lambda: lrn.PredictLinks(nodes, exclude=("test",))):
-        try:
-            bad()
-        except AmmsbError:
-            pass
-        else:
-            raise AssertionError("a bad argument was accepted")
+    ps.rejects(AmmsbError, (lambda: lrn.PredictLinks(nodes, top=0), lambda: lrn.PredictLinks(nodes, top=65),
+                            lambda: lrn.PredictLinks(nodes, exclude=("test",))))
     # slabs: a budget that cuts the queries into many calls gives the same tables
     every = np.arange(N - 1, -1, -7, dtype=np.uint32)
     one = tuple(t.cpu().numpy() for t in lrn.PredictLinks(every, top=4))
@@ -524,31 +476,13 @@ def learner_group(graph):
     assert np.array_equal(one[0], cut[0]) and np.array_equal(one[1].view(np.uint32), cut[1].view(np.uint32))
     lrn.close()
     # Run(20), all three calls, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.LinkProbabilities(he)
-    a.PredictLinks(nodes, top=10)
-    a.HeldoutAUC()
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + link prediction + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.LinkProbabilities(he)
+        a.PredictLinks(nodes, top=10)
+        a.HeldoutAUC()
+    ps.unperturbed_run(make, calls, "link prediction")
     print("learner ok graph=%s" % graph, flush=True)
-
-
-def _pi_beta_of_checkpoint(data, N, K):
-    from readout_child import _records
-    recs = _records(data)   # beta, theta, RpmProperties, the blocks of pi, ... (learner.cc:316-329)
-    beta, raw = recs[0], recs[3]
-    assert len(raw) >= N * K * 4 and len(recs[2]) < 64 and len(beta) >= 2 * K * 4
-    return (np.frombuffer(raw[len(raw) - N * K * 4:], dtype=np.float32).reshape(N, K),
-            np.frombuffer(beta[len(beta) - 2 * K * 4:], dtype=np.float32))
 
 
 def _check_links_file(path, ckpt, K, top, exclude, complete, nodes=None):
@@ -562,7 +496,7 @@ def _check_links_file(path, ckpt, K, top, exclude, complete, nodes=None):
     assert (fK, ftop, fex) == (K, top, exclude), (fK, ftop, fex)
     if nodes is not None:
         assert np.array_equal(fnodes, nodes)
-    pi, beta = _pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
+    pi, beta = ps.pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
     # every %.9g score parses back to a binary32: the text is exact
     p, bound = p64_block(pi, beta, EPS, fnodes.astype(np.int64), np.arange(fN))
     for i, a in enumerate(fnodes):
@@ -584,14 +518,10 @@ def _check_links_file(path, ckpt, K, top, exclude, complete, nodes=None):
 
 
 def cpp_group():
-    import subprocess
     import tempfile
     from mcmc_ammsb_gpu_amd import hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "linkpred_test"), d], capture_output=True, text=True, timeout=900)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("linkpred_test", d, 900)
         # cross-host: the file mcmc::Learner::WritePredictedLinks wrote against the checkpoint's pi.  (The exclusion
         # sets live in that process; eligibility beyond "not itself" was checked there.)
         fN, fnodes = _check_links_file(os.path.join(d, "links.txt"), os.path.join(d, "cpp.ckpt"), 64, 10, "all", None, None) \
@@ -599,7 +529,7 @@ def cpp_group():
         from mcmc_ammsb_gpu_amd import _linkpred
         fN, fK, ftop, fex, fnodes, ids, scores = _linkpred.read_links(os.path.join(d, "links.txt"))
         assert (fN, fK, ftop, fex, fnodes.size) == (20000, 64, 10, "all", 151)
-        pi, beta = _pi_beta_of_checkpoint(open(os.path.join(d, "cpp.ckpt"), "rb").read(), fN, fK)
+        pi, beta = ps.pi_beta_of_checkpoint(open(os.path.join(d, "cpp.ckpt"), "rb").read(), fN, fK)
         keep = ids != NONE
         assert keep.all() and not (ids == fnodes[:, None]).any()
         p, bound = p64_block(pi, beta, EPS, fnodes.astype(np.int64), np.arange(fN))
@@ -614,46 +544,32 @@ def cpp_group():
         out, ck, nf = os.path.join(d, "links.txt"), os.path.join(d, "main.ckpt"), os.path.join(d, "nodes.txt")
         some = np.array([5, 0, N - 1, 5, 4321], dtype=np.uint32)
         open(nf, "w").write("\n".join(str(v) for v in some) + "\n")
-        base = [os.path.join(pkg, "ammsb_main"), "--load-data", "1", "--load-file", f, "-k", "48", "-m", "256", "-n", "16",
-                "-x", "60", "-i", "30", "--links-out", out, "--checkpoint-out", ck]
+        base = ["--load-data", "1", "--load-file", f, "-k", "48", "-m", "256", "-n", "16", "-x", "60", "-i", "30",
+                "--links-out", out, "--checkpoint-out", ck]
         for extra, top, ex, nodes in (([], 10, "all", None),
                                       (["--links-top", "3", "--links-nodes", nf, "--links-exclude", "training"], 3, "training", some),
                                       (["--links-top", "64", "--links-nodes", nf, "--links-exclude", "none"], 64, "none", some)):
-            r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stderr[-3000:]
+            ps.run_ammsb_main(base + extra, 600)
             fN, fnodes = _check_links_file(out, ck, 48, top, ex, ex == "none", nodes)
             assert fN == N and (nodes is not None or np.array_equal(fnodes, np.arange(N)))
         # an id >= N in the node file is refused with status 2
         open(nf, "w").write("5\n%d\n" % N)
-        r = subprocess.run(base + ["--links-nodes", nf], capture_output=True, text=True, timeout=600)
-        assert r.returncode == 2 and ">= N" in r.stderr, r.stderr[-2000:]
+        r = ps.run_ammsb_main(base + ["--links-nodes", nf], 600, status=2)
+        assert ">= N" in r.stderr, r.stderr[-2000:]
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "accuracy":
-        accuracy_group(ks=KS if argv[1] == "all" else (int(argv[1]),))
-    elif kind == "selection":
-        selection_group()
-    elif kind == "layout":
-        layout_group()
-    elif kind == "forms":
-        forms_group()
-    elif kind == "big":
-        big_group()
-    elif kind == "planted":
-        planted_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "accuracy": lambda a: accuracy_group(ks=KS if a[0] == "all" else (int(a[0]),)),
+    "selection": lambda a: selection_group(),
+    "layout": lambda a: layout_group(),
+    "forms": lambda a: forms_group(),
+    "big": lambda a: big_group(),
+    "planted": lambda a: planted_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

@@ -6,7 +6,7 @@ import os
 import subprocess
 
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mcmc-ammsb-gpu_amd")
-DEVICE_LIBS = ("hip", "refsample", "readout", "linkpred", "linkcomm", "quality", "cover", "nmi", "omega")
+DEVICE_LIBS = ("hip", "refsample", "readout", "linkpred", "linkcomm", "quality", "cover", "nmi", "omega", "relate")
 
 
 @functools.lru_cache(maxsize=None)

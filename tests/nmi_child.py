@@ -21,18 +21,12 @@ import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
 NONE = 0xFFFFFFFF
-GUARD = 64                      # words past every output that must stay untouched
 FILL = -12345.678
 TOL = 2.0 ** -47
 INF = float("inf")
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 SEEN = set()
 F32 = np.float32
 
@@ -98,26 +92,15 @@ def slabbings(G):
     return {"whole": [(0, G)], "rows": [(g, g + 1) for g in range(G)], "ragged": list(zip(cuts[:-1], cuts[1:]))}
 
 
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import _nmi, ops
-        self.torch, self.ops, self.nm = torch, ops, _nmi
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
+        from mcmc_ammsb_gpu_amd import _nmi
+        super().__init__()
+        self.nm = _nmi
         self.lib = _nmi.load()
-        self.api = ops.CoverNMI(self.ctx)
-        self.cover = ops.CoverMatch(self.ctx)
-        self.ro = ops.CommunityReadout(self.ctx)
-
-    def matrix(self, host):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], 0)
-        pi.load(host)
-        return pi
-
-    def guarded(self, words):
-        buf = self.ctx.empty((words + GUARD,), self.torch.float64)
-        buf.fill_(FILL)
-        return buf
+        self.api = self.ops.CoverNMI(self.ctx)
+        self.cover = self.ops.CoverMatch(self.ctx)
+        self.ro = self.ops.CommunityReadout(self.ctx)
 
     def run(self, N, t, d, ov, slabs, misalign=False):
         """the library calls over buffers of this test's own, each followed by GUARD words that must survive; ov: a host
@@ -128,13 +111,13 @@ class Bench:
         d_t = self.ctx.from_numpy(np.ascontiguousarray(t, dtype=np.uint32))
         d_d = d if T.is_tensor(d) else self.ctx.from_numpy(np.ascontiguousarray(d, dtype=np.int64))
         flat = ov.reshape(-1) if T.is_tensor(ov) else self.ctx.from_numpy(np.ascontiguousarray(ov, dtype=np.uint32).reshape(-1))
-        store = self.ctx.empty((G * K + 1 + GUARD,), T.int32)
+        store = self.ctx.empty((G * K + 1 + ps.GUARD,), T.int32)
         store.fill_(0x5A5A5A5A)
         lead = 1 if misalign else 0   # 4 bytes past a 16-byte boundary
         store[lead:lead + G * K].copy_(flat)
         base = store.data_ptr() + 4 * lead
         assert base % 16 == (4 if misalign else 0)
-        bufs = dict(HX=self.guarded(G), HY=self.guarded(K), cX=self.guarded(G), cY=self.guarded(K))
+        bufs = {n: self.guarded(words, T.float64, FILL) for n, words in (("HX", G), ("HY", K), ("cX", G), ("cY", K))}
         ptr = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
         self.nm.check(self.lib.ammsb_nmi_begin(N, ptr(d_t), G, ptr(d_d), K, ptr(bufs["HX"]), ptr(bufs["HY"]),
                                                ptr(bufs["cX"]), ptr(bufs["cY"]), None))
@@ -344,7 +327,7 @@ def forms_group():
         mis = b.run(N, t, d, ov, [(0, 10), (10, G)], misalign=True)
         assert b.nm.last_kernel_name() == "nmi_generic", (K, b.nm.last_kernel_name())
         assert same_bits(got, mis), "K=%d: the misaligned base gives other bits" % K
-    src = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_nmi.hip")).read()
+    src = open(os.path.join(ps.ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_nmi.hip")).read()
     in_source = set(re.findall(r'"(nmi_[a-z0-9_]+)"', src))
     print("forms seen: %s" % " ".join(sorted(SEEN)), flush=True)
     assert SEEN == in_source == set(b.nm.KERNEL_FORMS)
@@ -396,23 +379,16 @@ def _check_nmi(r, host, thr, off, mem, what):
 
 
 def learner_group(graph):
-    from linkpred_child import _pi_beta_of_checkpoint, _same_buffers
-    from readout_child import _sample_buffers
     from mcmc_ammsb_gpu_amd import _nmi, hostlib
     from mcmc_ammsb_gpu_amd._capi import AmmsbError
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     off, mem = hostlib.generate_cover(N, k_true, seed=20260101)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
     lrn = make()
     lrn.Run(30)
     ck = io.BytesIO()
     lrn.Serialize(ck)
-    host, _ = _pi_beta_of_checkpoint(ck.getvalue(), N, K)
+    host, _ = ps.pi_beta_of_checkpoint(ck.getvalue(), N, K)
     lists = [mem[int(off[g]):int(off[g + 1])].tolist() for g in range(k_true)]
     for thr in (0.05, 0.01, 0.0, 2.0):
         first = None
@@ -436,42 +412,26 @@ def learner_group(graph):
     for none in ([], [[], []], (np.zeros(1, np.uint64), np.zeros(0, np.uint32))):
         r = lrn.CoverNMI(none, 0.05)
         assert r.nmi_lfk == -1.0 and not r.H_truth.any() and r.H_detected.size == K
-    for bad, err in ((lambda: lrn.CoverNMI(lists, -1.0), AmmsbError), (lambda: lrn.CoverNMI(lists, float("nan")), AmmsbError),
-                     (lambda: lrn.CoverNMI((np.array([0, 9]), mem[:3])), AmmsbError),
-                     (lambda: lrn.CoverNMI([[1, 2, 1]]), ValueError)):
-        try:
-            bad()
-        except err:
-            pass
-        else:
-            raise AssertionError("a bad argument was accepted")
+    ps.rejects(AmmsbError, (lambda: lrn.CoverNMI(lists, -1.0), lambda: lrn.CoverNMI(lists, float("nan")),
+                            lambda: lrn.CoverNMI((np.array([0, 9]), mem[:3]))))
+    ps.rejects(ValueError, (lambda: lrn.CoverNMI([[1, 2, 1]]),))
     lrn.close()
     # Run(20), the calls, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.CoverNMI((off, mem))
-    a.CoverNMI(lists, 0.01, slab_bytes=1)
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + cover NMI + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.CoverNMI((off, mem))
+        a.CoverNMI(lists, 0.01, slab_bytes=1)
+    ps.unperturbed_run(make, calls, "cover NMI")
     print("learner ok graph=%s" % graph, flush=True)
 
 
 def _check_nmi_file(path, ckpt, K, thr, offsets, members, what):
     """a cover-NMI file against the statement over the pi of the checkpoint the same process wrote; the Python writer
     reproduces its bytes, the scores in the header line included"""
-    from linkpred_child import _pi_beta_of_checkpoint
     from mcmc_ammsb_gpu_amd import _nmi
     fN, r, printed = _nmi.read_cover_nmi(path)
     assert r.H_detected.size == K and F32(r.threshold) == F32(thr), (r.H_detected.size, r.threshold)
-    pi, _ = _pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
+    pi, _ = ps.pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
     _check_nmi(r, pi, thr, offsets, members, what)
     assert printed == (r.nmi_lfk, r.nmi_max), (what, printed, r.nmi_lfk, r.nmi_max)
     again = path + ".py"
@@ -481,16 +441,11 @@ def _check_nmi_file(path, ckpt, K, thr, offsets, members, what):
 
 
 def cpp_group():
-    import subprocess
     import tempfile
     from cover_child import _check_match_file
     from mcmc_ammsb_gpu_amd import _cover, hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
-    main = os.path.join(pkg, "ammsb_main")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "nmi_test"), d], capture_output=True, text=True, timeout=240)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("nmi_test", d, 240)
         lists = [[int(w) for w in ln.split()[1:]] for ln in open(os.path.join(d, "truth.txt"))]
         offsets, members = _cover.check_cover(lists)
         fN, res = _check_nmi_file(os.path.join(d, "nmi.txt"), os.path.join(d, "cpp.ckpt"), 64, 0.05, offsets, members, "nmi_test")
@@ -508,18 +463,15 @@ def cpp_group():
         tail = ["-k", "48", "-m", "256", "-n", "16", "-x", "60", "-i", "30", "--ground-truth", truth, "--checkpoint-out", ck]
         for extra, thr in ((["--cover-nmi-out", out], 0.05),
                            (["--cover-nmi-out", out, "--cover-match-out", mout, "--cover-match-threshold", "0.01"], 0.01)):
-            r = subprocess.run([main, "--load-data", "1", "--load-file", f] + tail + extra, capture_output=True, text=True,
-                               timeout=240)
-            assert r.returncode == 0, r.stderr[-3000:]
+            ps.run_ammsb_main(["--load-data", "1", "--load-file", f] + tail + extra, 240)
             fN, res = _check_nmi_file(out, ck, 48, thr, toff, tmem, "ammsb_main dump thr=%g" % thr)
             assert fN == N and res.H_truth.size == 8 and res.skipped == 0
         _check_match_file(mout, ck, 48, 0.01, toff, tmem, "ammsb_main dump: the cover match beside the NMI")
         # --cover-match-out alone still works, unchanged
         os.remove(mout)
         os.remove(out)
-        r = subprocess.run([main, "--load-data", "1", "--load-file", f] + tail + ["--cover-match-out", mout],
-                           capture_output=True, text=True, timeout=240)
-        assert r.returncode == 0 and not os.path.exists(out), r.stderr[-3000:]
+        r = ps.run_ammsb_main(["--load-data", "1", "--load-file", f] + tail + ["--cover-match-out", mout], 240)
+        assert not os.path.exists(out), r.stderr[-3000:]
         _check_match_file(mout, ck, 48, 0.05, toff, tmem, "ammsb_main dump: --cover-match-out alone")
         # ... and on a text graph whose ids are not dense: the ground truth speaks of the file's ids
         name = lambda v: 7 * int(v) + 100     # noqa: E731
@@ -537,38 +489,25 @@ def cpp_group():
                 fh.write(" ".join("%d" % a for a in mem + [3, 5][:g % 3]) + "\n")     # (3 and 5 are nobody's id)
         woff, wmem, dropped = _cover.read_cover(truth, dense_of)
         assert dropped > 0 and woff.size == 9
-        r = subprocess.run([main, "-f", txt] + tail + ["--cover-nmi-out", out], capture_output=True, text=True, timeout=240)
-        assert r.returncode == 0, r.stderr[-3000:]
+        ps.run_ammsb_main(["-f", txt] + tail + ["--cover-nmi-out", out], 240)
         gN, res = _check_nmi_file(out, ck, 48, 0.05, woff, wmem, "ammsb_main text graph")
         assert gN == fN and res.H_truth.size == 8 and res.skipped == 0 and int(res.truth_size.sum()) == wmem.size
         # the three flag rules: status 2, before the graph is read
         for extra in (["--ground-truth", truth], ["--cover-nmi-out", out], ["--cover-match-out", mout]):
-            r = subprocess.run([main, "-f", os.path.join(d, "missing.txt"), "-k", "8"] + extra, capture_output=True,
-                               text=True, timeout=60)
-            assert r.returncode == 2 and "Failed to detect file" not in r.stderr, (extra, r.stderr[-500:])
+            r = ps.run_ammsb_main(["-f", os.path.join(d, "missing.txt"), "-k", "8"] + extra, 60, status=2)
+            assert "Failed to detect file" not in r.stderr, (extra, r.stderr[-500:])
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "exact":
-        exact_group(tuple(int(k) for k in argv[1:]) or (1, 3, 64, 65, 260, 1024, 1028, 8192))
-    elif kind == "planted":
-        planted_group()
-    elif kind == "forms":
-        forms_group()
-    elif kind == "persistent":
-        persistent_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "exact": lambda a: exact_group(tuple(int(k) for k in a) or (1, 3, 64, 65, 260, 1024, 1028, 8192)),
+    "planted": lambda a: planted_group(),
+    "forms": lambda a: forms_group(),
+    "persistent": lambda a: persistent_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

@@ -11,16 +11,10 @@ import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
 NONE = 0xFFFFFFFF
-GUARD = 64                      # words past every output that must stay untouched
 FILL32, FILL64 = 0x5A5A5A5A, 0x5A5A5A5A5A5A5A5A
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 SEEN = set()
 F32 = np.float32
 TILE = 128
@@ -76,44 +70,13 @@ def cuttings(total):
             "ragged": [(a, b - a) for a, b in zip(cuts[:-1], cuts[1:])]}
 
 
-class Raw:
-    """what ops.RowPartitionedMatrix shows of itself to ops.CoverOmega, over a descriptor of this test's own"""
-
-    def __init__(self, desc, cols, keep):
-        self.desc, self.cols, self.keep = desc, cols, keep
-
-
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import _omega, ops
-        self.torch, self.ops, self.om = torch, ops, _omega
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
+        from mcmc_ammsb_gpu_amd import _omega
+        super().__init__()
+        self.om = _omega
         self.lib = _omega.load()
-        self.api = ops.CoverOmega(self.ctx)
-
-    def matrix(self, host):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], 0)
-        pi.load(host)
-        return pi
-
-    def misaligned(self, host):
-        """one block whose base is 4 bytes past a 16-byte boundary"""
-        from mcmc_ammsb_gpu_amd._capi import Rpm
-        buf = self.ctx.empty((host.size + 1,), self.torch.float32)
-        buf[1:].copy_(self.ctx.from_numpy(host.reshape(-1)))
-        d = Rpm()
-        d.blocks[0] = buf.data_ptr() + 4
-        assert d.blocks[0] % 16 == 4
-        d.rows_in_block, d.num_rows, d.num_cols, d.num_blocks = host.shape[0], host.shape[0], host.shape[1], 1
-        return Raw(d, host.shape[1], buf)
-
-    def guarded(self, words, dtype, fill, zero=False):
-        buf = self.ctx.empty((words + GUARD,), dtype)
-        buf.fill_(fill)
-        if zero:
-            buf[:words].zero_()
-        return buf
+        self.api = self.ops.CoverOmega(self.ctx)
 
     def run(self, pi, thr, off, mem, U, cuts, L=None, identity=False):
         """the three library calls over buffers of this test's own, each followed by GUARD words that must survive"""
@@ -343,23 +306,16 @@ def _check_omega(r, host, thr, off, mem, U, what):
 
 
 def learner_group(graph):
-    from linkpred_child import _pi_beta_of_checkpoint, _same_buffers
-    from readout_child import _sample_buffers
     from mcmc_ammsb_gpu_amd import _omega, hostlib
     from mcmc_ammsb_gpu_amd._capi import AmmsbError
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     off, mem = hostlib.generate_cover(N, k_true, seed=20260101)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
     lrn = make()
     lrn.Run(30)
     ck = io.BytesIO()
     lrn.Serialize(ck)
-    host, _ = _pi_beta_of_checkpoint(ck.getvalue(), N, K)
+    host, _ = ps.pi_beta_of_checkpoint(ck.getvalue(), N, K)
     some = np.sort(np.random.default_rng(3).choice(N, 2000, replace=False)).astype(np.uint32)
     # a truth that covers a small share of the nodes: the planted cover of the nodes below 1500
     keep = mem < 1500
@@ -384,43 +340,27 @@ def learner_group(graph):
     assert (r.nodes, r.skipped, r.outside) == (0, 0, mem.size) and r.detected.tolist() == [0], r
     r = lrn.CoverOmega(wrong, 0.05, universe=some[:300])      # the same counts from the device
     assert (r.nodes, r.skipped, r.outside) == (300, 5, 0) and int(r.truth[0]) == 300 * 299 // 2, r
-    for bad, err in ((lambda: lrn.CoverOmega((off, mem), -1.0), AmmsbError),
-                     (lambda: lrn.CoverOmega((off, mem), universe=[5, 4]), AmmsbError),
-                     (lambda: lrn.CoverOmega((off, mem), universe=[1, N]), AmmsbError),
-                     (lambda: lrn.CoverOmega((off, mem), universe="all", max_bytes=1000), AmmsbError),
-                     (lambda: lrn.CoverOmega([[1, 2, 1]]), ValueError)):
-        try:
-            bad()
-        except err as e:
-            assert "max_bytes" not in str(e) or 'universe="covered"' in str(e)
-        else:
-            raise AssertionError("a bad argument was accepted")
+    refused = ps.rejects(AmmsbError, (lambda: lrn.CoverOmega((off, mem), -1.0), lambda: lrn.CoverOmega((off, mem), universe=[5, 4]),
+                                      lambda: lrn.CoverOmega((off, mem), universe=[1, N]),
+                                      lambda: lrn.CoverOmega((off, mem), universe="all", max_bytes=1000)))
+    refused += ps.rejects(ValueError, (lambda: lrn.CoverOmega([[1, 2, 1]]),))
+    assert len(refused) == 5 and all("max_bytes" not in str(e) or 'universe="covered"' in str(e) for e in refused)
     lrn.close()
     # Run(20), the call, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.CoverOmega((off, mem), universe=some)
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + cover omega + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.CoverOmega((off, mem), universe=some)
+    ps.unperturbed_run(make, calls, "cover omega")
     print("learner ok graph=%s" % graph, flush=True)
 
 
 def _check_omega_file(path, ckpt, K, thr, offsets, members, kind, what):
     """a cover-Omega file against the statement over the pi of the checkpoint the same process wrote; the Python writer
     reproduces its bytes, the scores in the header line included"""
-    from linkpred_child import _pi_beta_of_checkpoint
     from mcmc_ammsb_gpu_amd import _omega
     fN, r, printed = _omega.read_cover_omega(path)
     assert r.K == K and F32(r.threshold) == F32(thr) and r.G == offsets.size - 1, (r.K, r.G, r.threshold)
-    pi, _ = _pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
+    pi, _ = ps.pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
     U = _omega.check_universe(kind, fN, members)
     _check_omega(r, pi, thr, offsets, members, U, what)
     same_float = lambda a, b: a == b or (a != a and b != b)   # noqa: E731
@@ -432,17 +372,12 @@ def _check_omega_file(path, ckpt, K, thr, offsets, members, kind, what):
 
 
 def cpp_group():
-    import subprocess
     import tempfile
     from cover_child import _check_match_file
     from nmi_child import _check_nmi_file
     from mcmc_ammsb_gpu_amd import _cover, hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
-    main = os.path.join(pkg, "ammsb_main")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "omega_test"), d], capture_output=True, text=True, timeout=240)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("omega_test", d, 240)
         lists = [[int(w) for w in ln.split()[1:]] for ln in open(os.path.join(d, "truth.txt"))]
         offsets, members = _cover.check_cover(lists)
         fN, res = _check_omega_file(os.path.join(d, "omega.txt"), os.path.join(d, "cpp.ckpt"), 64, 0.05, offsets, members,
@@ -464,41 +399,27 @@ def cpp_group():
         for extra, thr, kind in ((["--cover-omega-out", out], 0.05, "covered"),
                                  (["--cover-omega-out", out, "--cover-omega-universe", "all", "--cover-match-threshold",
                                    "0.01"], 0.01, "all")):
-            r = subprocess.run([main, "--load-data", "1", "--load-file", f] + tail + extra, capture_output=True, text=True,
-                               timeout=240)
-            assert r.returncode == 0, r.stderr[-3000:]
+            ps.run_ammsb_main(["--load-data", "1", "--load-file", f] + tail + extra, 240)
             fN, res = _check_omega_file(out, ck, 48, thr, toff, tmem, kind, "ammsb_main dump universe=%s" % kind)
             assert fN == N and res.nodes == (N if kind == "all" else np.unique(tmem).size) and res.skipped == 0
         # --cover-match-out and --cover-nmi-out alone still work, unchanged
         os.remove(out)
         for flag, path, checker in (("--cover-match-out", mout, _check_match_file), ("--cover-nmi-out", nout, _check_nmi_file)):
-            r = subprocess.run([main, "--load-data", "1", "--load-file", f] + tail + [flag, path], capture_output=True,
-                               text=True, timeout=240)
-            assert r.returncode == 0 and not os.path.exists(out), r.stderr[-3000:]
+            r = ps.run_ammsb_main(["--load-data", "1", "--load-file", f] + tail + [flag, path], 240)
+            assert not os.path.exists(out), r.stderr[-3000:]
             checker(path, ck, 48, 0.05, toff, tmem, "ammsb_main dump: %s alone" % flag)
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "exact":
-        exact_group(tuple(int(i) for i in argv[1:]))
-    elif kind == "planted":
-        planted_group()
-    elif kind == "forms":
-        forms_group()
-    elif kind == "persistent":
-        persistent_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "exact": lambda a: exact_group(tuple(int(i) for i in a)),
+    "planted": lambda a: planted_group(),
+    "forms": lambda a: forms_group(),
+    "persistent": lambda a: persistent_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

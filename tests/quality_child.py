@@ -12,15 +12,9 @@ import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
 NONE = 0xFFFFFFFF
-GUARD = 64                      # words past every output that must stay untouched
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 SEEN = set()
 F32 = np.float32
 PLANTED = F32(0.125)                                   # a planted value: a threshold equal to its bits keeps it
@@ -105,42 +99,13 @@ def reference(pi, thr, edges):
     return counts, shared
 
 
-class Raw:
-    """a descriptor that is not a RowPartitionedMatrix: what the library call needs of one"""
-
-    def __init__(self, desc, cols, keep):
-        self.desc, self.cols, self.keep = desc, cols, keep
-
-
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import _quality, ops
-        self.torch, self.ops, self.q = torch, ops, _quality
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
+        from mcmc_ammsb_gpu_amd import _quality
+        super().__init__()
+        self.q = _quality
         self.lib = _quality.load()
-        self.api = ops.CommunityQuality(self.ctx)
-
-    def matrix(self, host, rows_in_block=0):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], rows_in_block)
-        pi.load(host)
-        return pi
-
-    def misaligned(self, host):
-        """one block whose base is 4 bytes past a 16-byte boundary"""
-        from mcmc_ammsb_gpu_amd._capi import Rpm
-        buf = self.ctx.empty((host.size + 1,), self.torch.float32)
-        buf[1:].copy_(self.ctx.from_numpy(host.reshape(-1)))
-        d = Rpm()
-        d.blocks[0] = buf.data_ptr() + 4
-        assert d.blocks[0] % 16 == 4
-        d.rows_in_block, d.num_rows, d.num_cols, d.num_blocks = host.shape[0], host.shape[0], host.shape[1], 1
-        return Raw(d, host.shape[1], buf)
-
-    def guarded(self, words, dtype, fill):
-        buf = self.ctx.empty((words + GUARD,), dtype)
-        buf.fill_(fill)
-        return buf
+        self.api = self.ops.CommunityQuality(self.ctx)
 
     def mask(self, pi, thr):
         """the library call over a workspace of this test's own, followed by GUARD words that must survive
@@ -161,9 +126,7 @@ class Bench:
         t = self.torch
         n = int(edges.size)
         d_edges = self.ctx.from_numpy(np.ascontiguousarray(edges, dtype=np.uint64))
-        cnt = self.guarded(2 * K + 2, t.int64, 0x5A5A5A5A5A5A) if counts else None
-        if cnt is not None:
-            cnt[:2 * K + 2] = 0
+        cnt = self.guarded(2 * K + 2, t.int64, 0x5A5A5A5A5A5A, zero=True) if counts else None
         sh = self.guarded(n, t.int32, 0x5A5A5A5A) if shared else None
         ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None   # noqa: E731
         self.q.check(self.lib.ammsb_quality_edges(ptr(mask), N, K, ptr(d_edges), n, ptr(cnt), ptr(sh), None))
@@ -329,7 +292,7 @@ def forms_group():
         got = b.edges(mask, 300, K, edges)
         assert b.q.last_kernel_name() == "quality_edges_" + eform, (K, b.q.last_kernel_name())
         check(got, reference(host, 0.05, edges), "forms K=%d" % K)
-    src = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_quality.hip")).read()
+    src = open(os.path.join(ps.ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_quality.hip")).read()
     in_source = set(re.findall(r'"(quality_(?:mask|edges)_[a-z0-9_]+)"', src))
     assert in_source == set(_quality.KERNEL_FORMS), in_source ^ set(_quality.KERNEL_FORMS)
     print("forms seen: %s" % " ".join(sorted(SEEN)), flush=True)
@@ -374,22 +337,15 @@ def big_group():
 
 
 def learner_group(graph):
-    from linkpred_child import _pi_beta_of_checkpoint, _same_buffers
-    from readout_child import _sample_buffers
-    from mcmc_ammsb_gpu_amd import _quality, hostlib
+    from mcmc_ammsb_gpu_amd import _quality
     from mcmc_ammsb_gpu_amd._capi import AmmsbError
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     lrn = make()
     lrn.Run(30)
     ck = io.BytesIO()
     lrn.Serialize(ck)
-    host, _ = _pi_beta_of_checkpoint(ck.getvalue(), N, K)
+    host, _ = ps.pi_beta_of_checkpoint(ck.getvalue(), N, K)
     assert np.array_equal(host.view(np.uint32), lrn.pi.host().view(np.uint32))
     links = lrn.TrainingLinks().cpu().numpy().view(np.uint64)
     E = links.size
@@ -423,42 +379,26 @@ def learner_group(graph):
         assert (r.links, r.uncovered, r.skipped, r.coverage) == (0, 0, 0, -1.0) and (r.conductance == -1).all()
         assert r.internal.sum() == 0 and np.array_equal(r.size, lrn.CommunitySizes(0.05).cpu().numpy())
         assert lrn.SharedCommunities(none, 0.05).numel() == 0
-    for bad in (lambda: lrn.CommunityQuality(-1.0), lambda: lrn.CommunityQuality(float("nan")),
-                lambda: lrn.SharedCommunities(some, float("inf"))):
-        try:
-            bad()
-        except AmmsbError:
-            pass
-        else:
-            raise AssertionError("a bad argument was accepted")
+    ps.rejects(AmmsbError, (lambda: lrn.CommunityQuality(-1.0), lambda: lrn.CommunityQuality(float("nan")),
+                            lambda: lrn.SharedCommunities(some, float("inf"))))
     lrn.close()
     # Run(20), the calls, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.CommunityQuality()
-    a.CommunityQuality(0.01, some)
-    a.SharedCommunities(some, 0.05)
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + community quality + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.CommunityQuality()
+        a.CommunityQuality(0.01, some)
+        a.SharedCommunities(some, 0.05)
+    ps.unperturbed_run(make, calls, "community quality")
     print("learner ok graph=%s" % graph, flush=True)
 
 
 def _check_file(path, ckpt, K, thr):
     """a community-quality file against the numpy statement over the pi of the checkpoint the same process wrote and
     the links the file counts; the Python writer reproduces its bytes"""
-    from linkpred_child import _pi_beta_of_checkpoint
     from mcmc_ammsb_gpu_amd import _quality
     fN, fK, fE, fthr, unc, size, internal, boundary, cond, dens = _quality.read_community_quality(path)
     assert fK == K and F32(fthr) == F32(thr), (fK, fthr)
-    pi, _ = _pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
+    pi, _ = ps.pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
     again = path + ".py"
     _quality.write_community_quality(again, fN, fthr, size, internal, boundary, fE, unc)
     assert open(again, "rb").read() == open(path, "rb").read(), "the Python writer's bytes differ"
@@ -474,14 +414,10 @@ def _check_counts(pi, thr, links, got, what):
 
 
 def cpp_group():
-    import subprocess
     import tempfile
     from mcmc_ammsb_gpu_amd import _linkcomm, hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "quality_test"), d], capture_output=True, text=True, timeout=240)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("quality_test", d, 240)
         fN, fE, pi, got = _check_file(os.path.join(d, "quality.txt"), os.path.join(d, "cpp.ckpt"), 64, 0.05)
         assert fN == 20000 and fE > 100000
         links = _linkcomm.read_link_communities(os.path.join(d, "links.txt"))[4]
@@ -493,11 +429,10 @@ def cpp_group():
         f = os.path.join(d, "g.bin.gz")
         hostlib.dump_dataset(f, N, 0.02, hostlib.generate_graph(N, 8, 12, seed=3))
         out, lc, ck = os.path.join(d, "q.txt"), os.path.join(d, "lc.txt"), os.path.join(d, "main.ckpt")
-        base = [os.path.join(pkg, "ammsb_main"), "--load-data", "1", "--load-file", f, "-k", "48", "-m", "256", "-n", "16",
-                "-x", "60", "-i", "30", "--community-quality-out", out, "--link-communities-out", lc, "--checkpoint-out", ck]
+        base = ["--load-data", "1", "--load-file", f, "-k", "48", "-m", "256", "-n", "16", "-x", "60", "-i", "30",
+                "--community-quality-out", out, "--link-communities-out", lc, "--checkpoint-out", ck]
         for extra, thr in (([], 0.05), (["--community-quality-threshold", "0.01"], 0.01)):
-            r = subprocess.run(base + extra, capture_output=True, text=True, timeout=240)
-            assert r.returncode == 0, r.stderr[-3000:]
+            ps.run_ammsb_main(base + extra, 240)
             fN, fE, pi, got = _check_file(out, ck, 48, thr)
             links = _linkcomm.read_link_communities(lc)[4]
             assert fN == N and fE == links.size and fE > 1000
@@ -505,28 +440,16 @@ def cpp_group():
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "exact":
-        exact_group(tuple(int(k) for k in argv[1:]) or (1, 3, 64, 65, 100, 256, 260, 1024, 2048, 8192))
-    elif kind == "persistent":
-        persistent_group(tuple(int(k) for k in argv[1:]) or (64, 256, 1024, 2048, 8192))
-    elif kind == "layout":
-        layout_group()
-    elif kind == "forms":
-        forms_group()
-    elif kind == "big":
-        big_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "exact": lambda a: exact_group(tuple(int(k) for k in a) or (1, 3, 64, 65, 100, 256, 260, 1024, 2048, 8192)),
+    "persistent": lambda a: persistent_group(tuple(int(k) for k in a) or (64, 256, 1024, 2048, 8192)),
+    "layout": lambda a: layout_group(),
+    "forms": lambda a: forms_group(),
+    "big": lambda a: big_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

@@ -2,26 +2,19 @@
 ops.CommunityReadout, Learner.Memberships / CommunitySizes / Communities, mcmc::Learner::Memberships,
 ammsb_main --communities-out) against a numpy statement, exactly: ids, count and sizes as integers, weights by bit
 pattern.  No tolerance appears anywhere."""
-import io
 import os
 import struct
-import subprocess
 import sys
 import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
 NONE = 0xFFFFFFFF
 KS = (1, 3, 48, 64, 113, 256, 512, 1024, 2048, 4096, 8192)
 TS = (1, 4, 16)
 ROWS = (1, 63, 65, 5000)
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 
 
 def sort_order(pi):
@@ -74,18 +67,10 @@ def draw(rng, n, K, kind):
     return (g / g.sum(1, keepdims=True, dtype=np.float32)).astype(np.float32)
 
 
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import ops
-        self.torch, self.ops = torch, ops
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
-        self.ro = ops.CommunityReadout(self.ctx)
-
-    def matrix(self, host, rows_in_block=0):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], rows_in_block)
-        pi.load(host)
-        return pi
+        super().__init__()
+        self.ro = self.ops.CommunityReadout(self.ctx)
 
     def run(self, pi, T, thr, **kw):
         sizes = self.ctx.zeros((pi.cols,), self.torch.int64)
@@ -231,59 +216,11 @@ def big_group():
     print("big ok: %d x %d (%.1f GB), sizes sum %d" % (n, K, n * K * 4 / 1e9, int(want.sum())), flush=True)
 
 
-def _records(data):
-    recs, pos = [], 0
-    while pos < len(data):
-        (n,) = struct.unpack_from("<Q", data, pos)
-        recs.append(data[pos + 8:pos + 8 + n])
-        pos += 8 + n
-    assert pos == len(data)
-    return recs
-
-
-def _same_buffers(a, b, what, partly=()):
-    """Every buffer record byte for byte (the short records carry accumulated device times, as in
-    tests/test_gpu_pi_placement.py).  partly: [(record, bytes of the buffer, bytes the pending mini-batch holds)] for
-    the per-sample device buffers, which are allocated uninitialised and written up to the mini-batch's size only: the
-    bytes past it were never written by either run and are whatever the allocator handed out."""
-    ra, rb = _records(a), _records(b)
-    assert len(ra) == len(rb) and sum(len(x) >= 200 for x in ra) >= 6, what
-    cut = {}
-    for i, total, valid in partly:
-        head = len(ra[i]) - total
-        assert 2 <= head <= 11 and valid <= total, (what, i, len(ra[i]), total)
-        cut[i] = head + valid
-    for i, (x, y) in enumerate(zip(ra, rb)):
-        assert len(x) == len(y), (what, i)
-        if len(x) >= 200:
-            n = cut.get(i, len(x))
-            assert x[:n] == y[:n], "%s: record %d (%d bytes) differs" % (what, i, len(x))
-
-
-def _sample_buffers(lrn):
-    """records of the per-sample device buffers in Learner.Serialize's order (13 records precede the first Sample:
-    beta, theta, pi's properties and block, phi, 2 + 3 operator records, 2 perplexity records, the learner's properties;
-    a Sample is its message, dev_edges, dev_nodes, the neighbour streams, the neighbour data)"""
-    assert lrn.trainingPerplexity is None and len(lrn.pi.blocks) == 1
-    out, n = [], lrn.cfg.num_node_sample
-    for i, s in enumerate(lrn.samples):
-        base = 13 + 5 * i
-        data = s.neighbor_sampler.GetData()
-        out += [(base + 1, s.dev_edges.numel() * 8, s.n_edges * 8), (base + 2, s.dev_nodes.numel() * 4, s.n_nodes * 4),
-                (base + 4, data.numel() * 4, s.n_nodes * n * 4)]
-    return out
-
-
 def learner_group(graph):
     import torch
-    from mcmc_ammsb_gpu_amd import _readout, hostlib
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
+    from mcmc_ammsb_gpu_amd import _readout
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     lrn = make()
     assert (lrn.loop is not None) == graph
     lrn.Run(30)
@@ -309,38 +246,20 @@ def learner_group(graph):
          expected(lrn.pi.host()[::-1], 4, 0.05), "Memberships of a node list in slabs")
     lrn.close()
     # Run(20), read-out, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.Memberships(4, 0.05)
-    a.CommunitySizes(0.05)
-    a.Communities(2, 0.1)
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + read-out + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.Memberships(4, 0.05)
+        a.CommunitySizes(0.05)
+        a.Communities(2, 0.1)
+    ca, cb = ps.unperturbed_run(make, calls, "read-out")
+    assert [len(x) for x in ps.records(ca)] == [len(y) for y in ps.records(cb)]   # the short records included
     print("learner ok graph=%s" % graph, flush=True)
-
-
-def _pi_of_checkpoint(data, N, K):
-    recs = _records(data)   # beta, theta, RpmProperties, the blocks of pi, ... (learner.cc:316-329)
-    raw = recs[3]
-    assert len(raw) >= N * K * 4 and len(recs[2]) < 64
-    return np.frombuffer(raw[len(raw) - N * K * 4:], dtype=np.float32).reshape(N, K)
 
 
 def cpp_group():
     from mcmc_ammsb_gpu_amd import _readout, hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "readout_test"), d], capture_output=True, text=True, timeout=900)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("readout_test", d, 900)
         # bit-level cross-host check through the checkpoint: pi parsed here, the numpy statement applied
         raw = open(os.path.join(d, "memberships.bin"), "rb").read()
         N, K, top = struct.unpack_from("<III", raw, 0)
@@ -354,7 +273,7 @@ def cpp_group():
         pos += N * 4
         sizes = np.frombuffer(raw, np.uint64, K, pos)
         assert pos + 8 * K == len(raw)
-        pi = _pi_of_checkpoint(open(os.path.join(d, "cpp.ckpt"), "rb").read(), N, K)
+        pi = ps.pi_beta_of_checkpoint(open(os.path.join(d, "cpp.ckpt"), "rb").read(), N, K)[0]
         wi, ww, wc, ws = expected(pi, top, thr)
         assert np.array_equal(ids, wi) and np.array_equal(weights.view(np.uint32), ww.view(np.uint32))
         assert np.array_equal(count, wc) and np.array_equal(sizes.astype(np.int64), ws)
@@ -369,10 +288,8 @@ def cpp_group():
         hostlib.dump_dataset(f, N, 0.02, hostlib.generate_graph(N, 8, 12, seed=3))
         out, ck = os.path.join(d, "comm.txt"), os.path.join(d, "main.ckpt")
         for extra, top, thr in (([], 4, 0.0), (["--membership-top", "2", "--membership-threshold", "0.1"], 2, 0.1)):
-            r = subprocess.run([os.path.join(pkg, "ammsb_main"), "--load-data", "1", "--load-file", f, "-k", "48", "-m", "256",
-                                "-n", "16", "-x", "60", "-i", "30", "--communities-out", out, "--checkpoint-out", ck] + extra,
-                               capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stderr[-3000:]
+            ps.run_ammsb_main(["--load-data", "1", "--load-file", f, "-k", "48", "-m", "256", "-n", "16", "-x", "60", "-i", "30",
+                               "--communities-out", out, "--checkpoint-out", ck] + extra, 600)
             fN, fK, ftop, fthr, fsizes, off, mem = _readout.read_communities(out)
             assert (fN, fK, ftop) == (N, 48, top) and np.float32(fthr) == np.float32(thr)
             per_node = np.bincount(mem, minlength=N)
@@ -381,32 +298,21 @@ def cpp_group():
                 mk = mem[off[k]:off[k + 1]]
                 assert fsizes[k] >= mk.size and (np.diff(mk) > 0).all() and (mk.size == 0 or (0 <= mk[0] and mk[-1] < N))
             # ... and against the pi of the checkpoint written by the same process
-            wi, _, _, ws = expected(_pi_of_checkpoint(open(ck, "rb").read(), N, 48), top, thr)
+            wi, _, _, ws = expected(ps.pi_beta_of_checkpoint(open(ck, "rb").read(), N, 48)[0], top, thr)
             woff, wmem = _readout.communities_csr(wi, 48)
             assert np.array_equal(fsizes, ws) and np.array_equal(off, woff) and np.array_equal(mem, wmem)
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "shapes":
-        shapes_group(argv[1])
-    elif kind == "layout":
-        layout_group()
-    elif kind == "ties":
-        ties_group()
-    elif kind == "big":
-        big_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "shapes": lambda a: shapes_group(a[0]),
+    "layout": lambda a: layout_group(),
+    "ties": lambda a: ties_group(),
+    "big": lambda a: big_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

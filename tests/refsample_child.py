@@ -2,16 +2,11 @@
 device sampler against the reference-exact host sampler (hostlib.Dataset.sample == host/sample.cc), bit for bit."""
 import ctypes as C
 import io
-import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
 HUB, HUB_DEGREE = 77, 5000
 U32 = np.uint64(0xFFFFFFFF)
@@ -257,9 +252,6 @@ def shortfall_group():
     print("shortfall ok", flush=True)
 
 
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32), "C2": (100_000, 256, 8192, 32, 32, 64)}   # bench.py's C1, C2
-
-
 def _state(lrn):
     import torch
     lrn.drain()
@@ -275,16 +267,10 @@ def _same(a, b, what):
 
 
 def trajectory_group(workload, parallel):
-    from mcmc_ammsb_gpu_amd import hostlib
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS[workload]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
+    _, learner = ps.c1_learner(False, workload)
 
     def make(ref):
-        cfg = Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                       sample_parallel=parallel, device_sampling=ref,
-                                       sampling_stream="reference" if ref else "own")
-        lrn = Learner(cfg, ds)
+        lrn = learner(sample_parallel=parallel, device_sampling=ref, sampling_stream="reference" if ref else "own")
         assert lrn.loop is None and (lrn.ref_sampler is not None) == ref and lrn.dev_sampler is None
         return lrn
     first, second = 30, 30
@@ -315,22 +301,13 @@ def trajectory_group(workload, parallel):
     print("trajectory ok %s parallel=%s: %d steps, perplexity %.6f" % (workload, parallel, first + second, ppx), flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "cpu-check":
-        cpu_check(argv[1:] or sorted(CASES))
-    elif kind == "sampler":
-        sampler_group(argv[1])
-    elif kind == "shortfall":
-        shortfall_group()
-    elif kind == "trajectory":
-        trajectory_group(argv[1], argv[2] == "1")
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "cpu-check": lambda a: cpu_check(a or sorted(CASES)),
+    "sampler": lambda a: sampler_group(a[0]),
+    "shortfall": lambda a: shortfall_group(),
+    "trajectory": lambda a: trajectory_group(a[0], a[1] == "1"),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

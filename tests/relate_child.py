@@ -15,15 +15,9 @@ from fractions import Fraction
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (ROOT, HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+import postfit_support as ps
 
-GUARD = 64                      # words past every output that must stay untouched
 FILL32, FILL64 = 0x5A5A5A5A, 0x5A5A5A5A5A5A5A5A
-WORKLOADS = {"C1": (10_000, 32, 1024, 32, 32, 32)}   # bench.py's C1
 SEEN = set()
 F32 = np.float32
 MEASURES = ("overlap", "jaccard", "contained")
@@ -83,45 +77,14 @@ def cuttings(N):
     return {"whole": [(0, N)], "slabs of 64": [(lo, min(lo + 64, N)) for lo in range(0, N, 64)], "ragged": ragged}
 
 
-class Raw:
-    """what ops.RowPartitionedMatrix shows of itself to ops.CommunityRelations, over a descriptor of this test's own"""
-
-    def __init__(self, desc, cols, keep):
-        self.desc, self.cols, self.keep = desc, cols, keep
-
-
-class Bench:
+class Bench(ps.DeviceBench):
     def __init__(self):
-        import torch
-        from mcmc_ammsb_gpu_amd import _relate, ops
-        self.torch, self.ops, self.rl = torch, ops, _relate
-        self.ctx = ops.Context(ops.make_params(1024, 32, E=1024))
+        from mcmc_ammsb_gpu_amd import _relate
+        super().__init__()
+        self.rl = _relate
         self.lib = _relate.load()
-        self.api = ops.CommunityRelations(self.ctx)
-        self.readout = ops.CommunityReadout(self.ctx)
-
-    def matrix(self, host, rows_in_block=0):
-        pi = self.ops.RowPartitionedMatrix(self.ctx, host.shape[0], host.shape[1], rows_in_block)
-        pi.load(host)
-        return pi
-
-    def misaligned(self, host):
-        """one block whose base is 4 bytes past a 16-byte boundary"""
-        from mcmc_ammsb_gpu_amd._capi import Rpm
-        buf = self.ctx.empty((host.size + 1,), self.torch.float32)
-        buf[1:].copy_(self.ctx.from_numpy(host.reshape(-1)))
-        d = Rpm()
-        d.blocks[0] = buf.data_ptr() + 4
-        assert d.blocks[0] % 16 == 4
-        d.rows_in_block, d.num_rows, d.num_cols, d.num_blocks = host.shape[0], host.shape[0], host.shape[1], 1
-        return Raw(d, host.shape[1], buf)
-
-    def guarded(self, words, dtype, fill, zero=False):
-        buf = self.ctx.empty((words + GUARD,), dtype)
-        buf.fill_(fill)
-        if zero:
-            buf[:words].zero_()
-        return buf
+        self.api = self.ops.CommunityRelations(self.ctx)
+        self.readout = self.ops.CommunityReadout(self.ctx)
 
     def overlap(self, pi, M, thr, cuts, what):
         """the bits and pair calls over guarded buffers of this test's own, slab by slab; every slab's words are
@@ -379,22 +342,15 @@ def _check_related(r, host, thr, by, top, min_overlap, what):
 
 def learner_group(graph):
     import torch
-    from linkpred_child import _pi_beta_of_checkpoint, _same_buffers
-    from readout_child import _sample_buffers
-    from mcmc_ammsb_gpu_amd import _relate, hostlib
+    from mcmc_ammsb_gpu_amd import _relate
     from mcmc_ammsb_gpu_amd._capi import AmmsbError
-    from mcmc_ammsb_gpu_amd.learner import Config, Learner
-    N, K, m, n, deg, k_true = WORKLOADS["C1"]
-    ds = hostlib.Dataset.robust(N, hostlib.generate_graph(N, k_true, deg, seed=20260101), heldout_ratio=0.01, rand_seed=1)
-
-    def make():
-        return Learner(Config.from_cli_defaults(K=K, mini_batch_size=m, num_node_sample=n, strategy="Node",
-                                                device_sampling=graph, graph_launch=graph), ds)
+    N, K, m, n, deg, k_true = ps.WORKLOADS["C1"]
+    ds, make = ps.c1_learner(graph)
     lrn = make()
     lrn.Run(30)
     ck = io.BytesIO()
     lrn.Serialize(ck)
-    host, _ = _pi_beta_of_checkpoint(ck.getvalue(), N, K)
+    host, _ = ps.pi_beta_of_checkpoint(ck.getvalue(), N, K)
     for thr in (0.05, 0.01):
         ov = lrn.CommunityOverlap(thr)
         assert ov.dtype == torch.int32 and tuple(ov.shape) == (K, K)
@@ -413,41 +369,25 @@ def learner_group(graph):
             assert cut.matrix is None and np.array_equal(cut.partner, r.partner) and np.array_equal(cut.overlap, r.overlap)
             assert np.array_equal(cut.size, r.size)
         print("thr=%g: %d of %d community pairs overlap" % (thr, int((np.triu(want, 1) > 0).sum()), K * (K - 1) // 2), flush=True)
-    for bad in (lambda: lrn.CommunityOverlap(-1.0), lambda: lrn.RelatedCommunities(top=65), lambda: lrn.RelatedCommunities(by="cosine"),
-                lambda: lrn.CommunityOverlap(max_bytes=0)):
-        try:
-            bad()
-        except AmmsbError:
-            pass
-        else:
-            raise AssertionError("a bad argument was accepted")
+    ps.rejects(AmmsbError, (lambda: lrn.CommunityOverlap(-1.0), lambda: lrn.RelatedCommunities(top=65), lambda: lrn.RelatedCommunities(by="cosine"),
+                            lambda: lrn.CommunityOverlap(max_bytes=0)))
     lrn.close()
     # Run(20), the calls, Run(20) leaves the state Run(40) leaves
-    a, bb = make(), make()
-    a.Run(20)
-    a.CommunityOverlap(0.05, max_bytes=1000)
-    a.RelatedCommunities()
-    a.Run(20)
-    bb.Run(40)
-    ca, cb = io.BytesIO(), io.BytesIO()
-    a.Serialize(ca)
-    bb.Serialize(cb)
-    assert [(s.n_edges, s.n_nodes) for s in a.samples] == [(s.n_edges, s.n_nodes) for s in bb.samples]
-    _same_buffers(ca.getvalue(), cb.getvalue(), "Run(20) + community relations + Run(20) against Run(40)", _sample_buffers(a))
-    assert a.HeldoutPerplexity() == bb.HeldoutPerplexity()
-    a.close()
-    bb.close()
+
+    def calls(a):
+        a.CommunityOverlap(0.05, max_bytes=1000)
+        a.RelatedCommunities()
+    ps.unperturbed_run(make, calls, "community relations")
     print("learner ok graph=%s" % graph, flush=True)
 
 
 def _check_related_file(path, ckpt, K, thr, by, top, what):
     """a related-communities file against the statement over the pi of the checkpoint the same process wrote; the
     Python writer reproduces its bytes"""
-    from linkpred_child import _pi_beta_of_checkpoint
     from mcmc_ammsb_gpu_amd import _relate
     fN, r = _relate.read_related(path)
     assert r.size.size == K and F32(r.threshold) == F32(thr) and (r.by, r.top, r.min_overlap) == (by, top, 1), what
-    pi, _ = _pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
+    pi, _ = ps.pi_beta_of_checkpoint(open(ckpt, "rb").read(), fN, K)
     _check_related(r, pi, thr, by, top, 1, what)
     again = path + ".py"
     _relate.write_related(again, fN, r)
@@ -456,15 +396,10 @@ def _check_related_file(path, ckpt, K, thr, by, top, what):
 
 
 def cpp_group():
-    import subprocess
     import tempfile
     from mcmc_ammsb_gpu_amd import hostlib
-    pkg = os.path.join(ROOT, "mcmc-ammsb-gpu_amd")
-    main = os.path.join(pkg, "ammsb_main")
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([os.path.join(pkg, "relate_test"), d], capture_output=True, text=True, timeout=240)
-        print(r.stdout[-3000:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+        ps.run_cpp_test("relate_test", d, 240)
         fN, res = _check_related_file(os.path.join(d, "related.txt"), os.path.join(d, "cpp.ckpt"), 64, 0.05, "jaccard", 4,
                                       "relate_test")
         assert fN == 20000
@@ -478,34 +413,21 @@ def cpp_group():
                                     (["--related-communities-threshold", "0.02", "--related-communities-top", "64",
                                       "--related-communities-by", "contained"], 0.02, "contained", 64),
                                     (["--related-communities-by", "overlap", "--related-communities-top", "1"], 0.05, "overlap", 1)):
-            r = subprocess.run([main, "--load-data", "1", "--load-file", f] + tail + ["--related-communities-out", out] + extra,
-                               capture_output=True, text=True, timeout=240)
-            assert r.returncode == 0, r.stderr[-3000:]
+            ps.run_ammsb_main(["--load-data", "1", "--load-file", f] + tail + ["--related-communities-out", out] + extra, 240)
             fN, res = _check_related_file(out, ck, 48, thr, by, top, "ammsb_main by=%s" % by)
             assert fN == N
         print("cli ok", flush=True)
 
 
-def main(argv):
-    import __graft_entry__ as ge
-    ge.build()
-    kind = argv[0]
-    if kind == "exact":
-        exact_group(tuple(int(i) for i in argv[1:]))
-    elif kind == "depth":
-        depth_group()
-    elif kind == "forms":
-        forms_group()
-    elif kind == "planted":
-        planted_group()
-    elif kind == "learner":
-        learner_group(argv[1] == "1")
-    elif kind == "cpp":
-        cpp_group()
-    else:
-        raise SystemExit("unknown group %r" % kind)
-    print("group ok", flush=True)
+GROUPS = {
+    "exact": lambda a: exact_group(tuple(int(i) for i in a)),
+    "depth": lambda a: depth_group(),
+    "forms": lambda a: forms_group(),
+    "planted": lambda a: planted_group(),
+    "learner": lambda a: learner_group(a[0] == "1"),
+    "cpp": lambda a: cpp_group(),
+}
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:])
+    ps.child_main(GROUPS, sys.argv[1:])

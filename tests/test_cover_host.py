@@ -12,6 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from postfit_support import exported_symbols
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 EINVAL = -1  # AMMSB_EINVAL
@@ -34,11 +36,7 @@ def test_header_exports_and_signature_table_agree(cv):
     lib = C.CDLL(cv.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    nm = next((p for p in ("/usr/bin/nm", "/opt/rocm/llvm/bin/llvm-nm", "/opt/rocm/lib/llvm/bin/llvm-nm") if os.path.exists(p)), None)
-    assert nm, "no nm / llvm-nm to list the library's symbols"
-    out = subprocess.run([nm, "-D", "--defined-only", cv.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in ("T", "t")}
-    own = {s for s in exported if not s.startswith(("_init", "_fini", "__hip", "_ZSt", "_ZNSt", "_ZNKSt"))}
+    own = exported_symbols(cv.LIB_PATH)
     assert own == declared, own ^ declared
     assert cv.MAX_COLS == int(re.search(r"#define AMMSB_COVER_MAX_COLS (\d+)u", hdr).group(1)) == 8192
     assert cv.UNIT == int(re.search(r"#define AMMSB_COVER_UNIT (\d+)u", hdr).group(1))

@@ -27,29 +27,15 @@ One child process per group (cover_child.py):
            pi of the checkpoint the same process wrote, for a data-set dump (dense ids) and for a text graph whose ids
            are not dense (mapped, the unknown ones dropped and counted); the Python writer's bytes match.
 """
-import os
-import subprocess
-import sys
+import functools
 
 import pytest
 
+from postfit_support import run_group
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CHILD = os.path.join(HERE, "cover_child.py")
-
-
-def _run(args, expect, timeout):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no fallback path exists)")
-    out = subprocess.run([sys.executable, CHILD] + args, capture_output=True, text=True, timeout=timeout,
-                         cwd=os.path.dirname(HERE))
-    if out.returncode != 0:
-        pytest.fail("group %r (exit %d):\n%s\n%s" % (args, out.returncode, out.stdout[-2000:], out.stderr[-5000:]),
-                    pytrace=False)
-    assert expect in out.stdout and "group ok" in out.stdout, out.stdout[-2000:]
-    print(out.stdout)
+_run = functools.partial(run_group, "cover_child.py")
 
 
 @pytest.mark.parametrize("ks", ["1 3 64 65 100", "256 260 1024", "2048", "8192"])

@@ -20,29 +20,15 @@ One child process per group (linkpred_child.py):
              under the bound, eligibility against the host sets), its links file against the pi of the checkpoint it
              wrote; ammsb_main --links-out parsed back and compared with the numpy statement over its checkpoint's pi.
 """
-import os
-import subprocess
-import sys
+import functools
 
 import pytest
 
+from postfit_support import run_group
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CHILD = os.path.join(HERE, "linkpred_child.py")
-
-
-def _run(args, expect, timeout=1500):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no fallback path exists)")
-    out = subprocess.run([sys.executable, CHILD] + args, capture_output=True, text=True, timeout=timeout,
-                         cwd=os.path.dirname(HERE))
-    if out.returncode != 0:
-        pytest.fail("group %r (exit %d):\n%s\n%s" % (args, out.returncode, out.stdout[-2000:], out.stderr[-5000:]),
-                    pytrace=False)
-    assert expect in out.stdout and "group ok" in out.stdout, out.stdout[-2000:]
-    print(out.stdout)
+_run = functools.partial(run_group, "linkpred_child.py", timeout=1500)
 
 
 def test_dense_and_pair_scores_meet_the_derived_bound():

@@ -17,29 +17,15 @@ One child process per group (readout_child.py):
   cpp      tests/cpp/readout_test.cc (mcmc::Learner::Memberships against GetPiRow), its memberships and communities file
            against the numpy statement over the pi of the checkpoint it wrote; ammsb_main --communities-out.
 """
-import os
-import subprocess
-import sys
+import functools
 
 import pytest
 
+from postfit_support import run_group
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CHILD = os.path.join(HERE, "readout_child.py")
-
-
-def _run(args, expect, timeout=1500):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no fallback path exists)")
-    out = subprocess.run([sys.executable, CHILD] + args, capture_output=True, text=True, timeout=timeout,
-                         cwd=os.path.dirname(HERE))
-    if out.returncode != 0:
-        pytest.fail("group %r (exit %d):\n%s\n%s" % (args, out.returncode, out.stdout[-2000:], out.stderr[-5000:]),
-                    pytrace=False)
-    assert expect in out.stdout and "group ok" in out.stdout, out.stdout[-2000:]
-    print(out.stdout)
+_run = functools.partial(run_group, "readout_child.py", timeout=1500)
 
 
 def test_every_shape_equals_the_numpy_statement():

@@ -13,31 +13,16 @@ One child process per group (refsample_child.py):
               and C2 (pi rows, beta, theta, phi sums, both Sample seeds, the perplexity), with
               sample_parallel on and off; each mode's mid-run checkpoint resumed in the other mode ends in the same state.
 """
-import os
-import subprocess
-import sys
+import functools
 
 import pytest
 
 import refsample_child as rc
+from postfit_support import run_group
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CHILD = os.path.join(HERE, "refsample_child.py")
-
-
-def _run(args, expect):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a HIP device (no fallback path exists)")
-    out = subprocess.run([sys.executable, CHILD] + args, capture_output=True, text=True, timeout=1500,
-                         cwd=os.path.dirname(HERE))
-    if out.returncode != 0:
-        pytest.fail("group %r (exit %d):\n%s\n%s" % (args, out.returncode, out.stdout[-2000:], out.stderr[-5000:]),
-                    pytrace=False)
-    assert expect in out.stdout and "group ok" in out.stdout, out.stdout[-2000:]
-    print(out.stdout)
+_run = functools.partial(run_group, "refsample_child.py", timeout=1500)
 
 
 @pytest.mark.parametrize("case", sorted(rc.CASES))

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from postfit_support import exported_symbols
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 EINVAL = -1  # AMMSB_EINVAL
@@ -33,11 +35,7 @@ def test_header_exports_and_signature_table_agree(q):
     lib = C.CDLL(q.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    nm = next((p for p in ("/usr/bin/nm", "/opt/rocm/llvm/bin/llvm-nm", "/opt/rocm/lib/llvm/bin/llvm-nm") if os.path.exists(p)), None)
-    assert nm, "no nm / llvm-nm to list the library's symbols"
-    out = subprocess.run([nm, "-D", "--defined-only", q.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in ("T", "t")}
-    own = {s for s in exported if not s.startswith(("_init", "_fini", "__hip", "_ZSt", "_ZNSt", "_ZNKSt"))}
+    own = exported_symbols(q.LIB_PATH)
     assert own == declared, own ^ declared
     assert q.MAX_COLS == int(re.search(r"#define AMMSB_QUALITY_MAX_COLS (\d+)u", hdr).group(1)) == 8192
     # the kernel forms: the names in the source are the names the signature module lists and the header describes

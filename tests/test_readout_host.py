@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from postfit_support import exported_symbols
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 EXE = os.environ.get("AMMSB_MAIN_EXE") or os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "ammsb_main")
@@ -33,11 +35,7 @@ def test_header_exports_and_signature_table_agree(ro):
     for name in declared:
         assert hasattr(lib, name), name
     # the library exports no other function of its own (kernel stubs are local: anonymous namespace)
-    nm = next((p for p in ("/usr/bin/nm", "/opt/rocm/llvm/bin/llvm-nm", "/opt/rocm/lib/llvm/bin/llvm-nm") if os.path.exists(p)), None)
-    assert nm, "no nm / llvm-nm to list the library's symbols"
-    out = subprocess.run([nm, "-D", "--defined-only", ro.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if len(ln.split()) >= 3 and ln.split()[-2] in ("T", "t")}
-    own = {s for s in exported if not s.startswith(("_init", "_fini", "__hip", "_ZSt", "_ZNSt", "_ZNKSt"))}
+    own = exported_symbols(ro.LIB_PATH)
     assert own == declared, own ^ declared
     assert (ro.MAX_TOP, ro.MAX_COLS) == tuple(int(re.search(r"#define %s (\d+)u" % n, hdr).group(1))
                                               for n in ("AMMSB_READOUT_MAX_TOP", "AMMSB_READOUT_MAX_COLS"))
