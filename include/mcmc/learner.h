@@ -182,6 +182,30 @@ class Learner {
   bool WriteRelatedCommunities(std::ostream* out, Float threshold, uint32_t top, const std::string& by,
                                uint32_t min_overlap = 1, uint64_t max_bytes = 1ull << 30);
 
+  // How the detected communities are linked to each other (include/ammsb_connect.h), over the training links (every link
+  // once as (min << 32) | max).  CommunityLinks: links[K * K] = directed + its transpose, directed[k, l] counting the
+  // links (a, b) with pi[a, k] >= threshold and pi[b, l] >= threshold; symmetric, the diagonal is twice CommunityQuality's
+  // internal.  LinkedCommunities: per community the `top` (1..64) others with at least max(1, min_links) links to it,
+  // ranked by `by` -- "links" (the count w) or "density" (w over the d_k d_l - overlap[k, l] ordered pairs of distinct
+  // nodes; no such pair: no partner) -- as exact rationals, equal values by id ascending; the overlap is
+  // CommunityOverlap(threshold, max_bytes).  std::invalid_argument on a bad threshold, measure or top.  Waits, reads and
+  // perturbs like CommunityQuality.
+  struct Linked {
+    std::vector<uint64_t> size;      // [K]
+    std::vector<uint64_t> internal;  // [K], the links inside k
+    std::vector<int32_t> partner;    // [K * top], -1 in an empty slot
+    std::vector<uint64_t> links;     // [K * top], the links between k and that partner, 0 in an empty slot
+    std::vector<uint32_t> shared;    // [K * top], the nodes shared with that partner, 0 in an empty slot
+    uint64_t valid = 0, skipped = 0; // the training links counted; those with an end >= N (none)
+  };
+  void CommunityLinks(Float threshold, std::vector<uint64_t>* links);
+  void LinkedCommunities(Float threshold, uint32_t top, const std::string& by, uint64_t min_links, Linked* linked,
+                         uint64_t max_bytes = 1ull << 30);
+  // `# N K E threshold by top min_links skipped`, then `k size internal n l0 w0 o0 l1 w1 o1 ...` per community: integers
+  // below the header.
+  bool WriteLinkedCommunities(std::ostream* out, Float threshold, uint32_t top, const std::string& by,
+                              uint64_t min_links = 1, uint64_t max_bytes = 1ull << 30);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

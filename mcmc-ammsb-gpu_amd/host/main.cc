@@ -77,12 +77,16 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy;
   bool haveCoverThreshold = false;
   double coverThreshold = 0.05;
   bool haveRelatedThreshold = false, haveRelatedTop = false;
   double relatedThreshold = 0.05;
   long relatedTop = 4;
+  bool haveLinkedThreshold = false, haveLinkedTop = false, haveLinkedMinLinks = false;
+  double linkedThreshold = 0.05;
+  long linkedTop = 4;
+  long long linkedMinLinks = 1;
   bool haveQualityThreshold = false;
   double qualityThreshold = 0.05;
   bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
@@ -211,6 +215,29 @@ int main(int argc, char** argv) {
                return !in.fail() && in.eof();
              }},
       OptStr("related-communities-by", 0, &relatedBy),  // (new, with --related-communities-out) jaccard (default) | overlap | contained
+      OptStr("linked-communities-out", 0, &linkedOut),  // (new) after the last perplexity line: `# N K E threshold by top min_links skipped`, then `k size internal n l0 w0 o0 l1 w1 o1 ...` per community: the n other communities it is linked to most, the training links to each and the nodes shared with each
+      Option{"linked-communities-threshold", 0, "0.05 (new, with --linked-communities-out: a node is a member of k iff pi[a, k] >= it)",
+             [&](const std::string& v) {
+               haveLinkedThreshold = true;
+               std::istringstream in(v);
+               in >> linkedThreshold;
+               return !in.fail() && in.eof();
+             }},
+      Option{"linked-communities-top", 0, "4 (new, with --linked-communities-out: partners kept per community, 1..64)",
+             [&](const std::string& v) {
+               haveLinkedTop = true;
+               std::istringstream in(v);
+               in >> linkedTop;
+               return !in.fail() && in.eof();
+             }},
+      OptStr("linked-communities-by", 0, &linkedBy),  // (new, with --linked-communities-out) density (default) | links
+      Option{"linked-communities-min-links", 0, "1 (new, with --linked-communities-out: fewest links that make a partner)",
+             [&](const std::string& v) {
+               haveLinkedMinLinks = true;
+               std::istringstream in(v);
+               in >> linkedMinLinks;
+               return !in.fail() && in.eof();
+             }},
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -311,6 +338,14 @@ int main(int argc, char** argv) {
   if (relatedTop < 1 || relatedTop > 64) Fatal("--related-communities-top must be in 1..64");
   if (!(relatedThreshold >= 0) || !std::isfinite(static_cast<float>(relatedThreshold)))
     Fatal("--related-communities-threshold must be finite and >= 0");
+  if ((haveLinkedThreshold || haveLinkedTop || haveLinkedMinLinks || !linkedBy.empty()) && linkedOut.empty())
+    Fatal("--linked-communities-threshold / --linked-communities-top / --linked-communities-by / --linked-communities-min-links need --linked-communities-out FILE");
+  if (!linkedBy.empty() && linkedBy != "density" && linkedBy != "links")
+    Fatal("--linked-communities-by must be density or links");
+  if (linkedTop < 1 || linkedTop > 64) Fatal("--linked-communities-top must be in 1..64");
+  if (!(linkedThreshold >= 0) || !std::isfinite(static_cast<float>(linkedThreshold)))
+    Fatal("--linked-communities-threshold must be finite and >= 0");
+  if (linkedMinLinks < 0) Fatal("--linked-communities-min-links must be >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -522,6 +557,21 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("related communities: ") + e.what());
+    }
+  }
+  if (!linkedOut.empty()) {
+    // every rank holds all of pi and the training links: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(linkedOut);
+        if (!out.good() || !learner.WriteLinkedCommunities(&out, static_cast<mcmc::Float>(linkedThreshold),
+                                                           static_cast<uint32_t>(linkedTop),
+                                                           linkedBy.empty() ? "density" : linkedBy,
+                                                           static_cast<uint64_t>(linkedMinLinks)))
+          Fatal("cannot write linked communities " + linkedOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("linked communities: ") + e.what());
     }
   }
   learner.PrintStats();

@@ -1,7 +1,7 @@
 // mcmc::Learner's post-fit analyses (include/mcmc/learner.h): what reads a fitted model out -- memberships and
 // communities, link prediction, link communities, community quality, the three comparisons with a ground-truth cover
-// (F1 match, overlapping NMI, Omega index), and how the detected communities relate to each other.  Each is a thin driver
-// of one library of its own (libammsb_readout.so ... libammsb_relate.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
+// (F1 match, overlapping NMI, Omega index), how the detected communities relate to each other and how they are linked.  Each is
+// a thin driver of one library of its own (libammsb_readout.so ... libammsb_connect.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
 // read the results back, and for the Write* methods print them.  Nothing here touches the training loop of learner.cc.
 #include "mcmc/learner.h"
 #include "ammsb_readout.h"
@@ -12,6 +12,7 @@
 #include "ammsb_nmi.h"
 #include "ammsb_omega.h"
 #include "ammsb_relate.h"
+#include "ammsb_connect.h"
 
 #include <hip/hip_runtime.h>
 
@@ -766,6 +767,113 @@ bool Learner::WriteRelatedCommunities(std::ostream* out, Float threshold, uint32
     while (n < top && r.partner[k * top + n] >= 0) ++n;
     *out << k << " " << r.size[k] << " " << n;
     for (uint32_t t = 0; t < n; ++t) *out << " " << r.partner[k * top + t] << " " << r.overlap[k * top + t];
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- how the detected communities are linked to each other: libammsb_connect.so over pi and the training links
+namespace {
+uint32_t ConnectMeasure(const std::string& by) {
+  if (by == "links") return AMMSB_CONNECT_LINKS;
+  if (by == "density") return AMMSB_CONNECT_DENSITY;
+  throw std::invalid_argument("LinkedCommunities: the measure is \"links\" or \"density\", not \"" + by + "\"");
+}
+
+// links[K, K] and counts[2] on the device from the sorted training links; waits before it returns (the mask, the edge
+// list and the directed matrix are freed on return)
+void LinksOnDevice(const ammsb_rpm* pi, Float threshold, const std::vector<Edge>& edges, clcuda::Buffer<uint64_t>* d_links,
+                   clcuda::Buffer<uint64_t>* d_counts, const clcuda::Context& context, const clcuda::Queue& queue) {
+  const uint64_t N = pi->num_rows, K = pi->num_cols;
+  if (K == 0 || K > AMMSB_CONNECT_MAX_COLS) throw std::runtime_error("CommunityLinks: K outside 1..8192");
+  hipStream_t stream = static_cast<hipStream_t>(queue.stream());
+  clcuda::Buffer<uint64_t> d_directed(context, K * K);
+  hipError_t e = hipMemsetAsync(d_directed(), 0, K * K * sizeof(uint64_t), stream);
+  if (e == hipSuccess) e = hipMemsetAsync((*d_counts)(), 0, 2 * sizeof(uint64_t), stream);
+  if (e != hipSuccess) throw std::runtime_error(std::string("CommunityLinks: memset: ") + hipGetErrorString(e));
+  const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
+  clcuda::Buffer<uint64_t> d_mask(context, std::max<uint64_t>(words, 1));
+  std::unique_ptr<clcuda::Buffer<Edge>> d_edges;
+  int rc = AMMSB_OK;
+  if (!edges.empty() && N > 0) {
+    d_edges.reset(new clcuda::Buffer<Edge>(context, queue, edges.begin(), edges.end()));
+    rc = ammsb_connect_mask(pi, threshold, d_mask(), stream);
+    if (rc == AMMSB_OK)
+      rc = ammsb_connect_edges(d_mask(), N, static_cast<uint32_t>(K), (*d_edges)(), edges.size(), d_directed(),
+                               (*d_counts)(), stream);
+  }
+  if (rc == AMMSB_OK) rc = ammsb_connect_finish(d_directed(), static_cast<uint32_t>(K), (*d_links)(), stream);
+  if (rc != AMMSB_OK) throw PostfitError("ammsb_connect", rc, ammsb_connect_last_error());
+  e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) throw std::runtime_error(std::string("CommunityLinks: ") + hipGetErrorString(e));
+}
+}  // namespace
+
+void Learner::CommunityLinks(Float threshold, std::vector<uint64_t>* links) {
+  CheckThreshold("CommunityLinks", threshold);
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t K = pi_->Cols();
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint64_t> d_links(context, K * K), d_counts(context, 2);
+  LinksOnDevice(&pi_->Get(), threshold, SortedTrainingLinks(cfg_), &d_links, &d_counts, context, queue_);
+  links->resize(K * K);
+  d_links.Read(queue_, K * K, links->data());
+  queue_.Finish();
+}
+
+void Learner::LinkedCommunities(Float threshold, uint32_t top, const std::string& by, uint64_t min_links, Linked* linked,
+                                uint64_t max_bytes) {
+  CheckThreshold("LinkedCommunities", threshold);
+  const uint32_t measure = ConnectMeasure(by);
+  if (top == 0 || top > AMMSB_CONNECT_MAX_TOP) throw std::invalid_argument("LinkedCommunities: top must be in 1..64");
+  if (max_bytes < 1) throw std::invalid_argument("LinkedCommunities: max_bytes must be at least 1");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t K = pi_->Cols();
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint32_t> d_overlap(context, K * K), d_shared(context, K * top);
+  clcuda::Buffer<uint64_t> d_links(context, K * K), d_counts(context, 2), d_plinks(context, K * top);
+  clcuda::Buffer<int32_t> d_partner(context, K * top);
+  OverlapOnDevice(&pi_->Get(), threshold, max_bytes, &d_overlap, context, queue_.stream());
+  LinksOnDevice(&pi_->Get(), threshold, SortedTrainingLinks(cfg_), &d_links, &d_counts, context, queue_);
+  const int rc = ammsb_connect_top(d_links(), d_overlap(), static_cast<uint32_t>(K), measure, top, min_links, d_partner(),
+                                   d_plinks(), d_shared(), queue_.stream());
+  if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_top", rc, ammsb_connect_last_error());
+  linked->partner.resize(K * top);
+  linked->links.resize(K * top);
+  linked->shared.resize(K * top);
+  d_partner.Read(queue_, K * top, linked->partner.data());
+  d_plinks.Read(queue_, K * top, linked->links.data());
+  d_shared.Read(queue_, K * top, linked->shared.data());
+  std::vector<uint32_t> overlap(K * K);
+  std::vector<uint64_t> matrix(K * K), counts(2);
+  d_overlap.Read(queue_, K * K, overlap.data());
+  d_links.Read(queue_, K * K, matrix.data());
+  d_counts.Read(queue_, 2, counts.data());
+  queue_.Finish();
+  linked->size.resize(K);
+  linked->internal.resize(K);
+  for (uint64_t k = 0; k < K; ++k) {
+    linked->size[k] = overlap[k * K + k];
+    linked->internal[k] = matrix[k * K + k] / 2;
+  }
+  linked->valid = counts[0];
+  linked->skipped = counts[1];
+}
+
+bool Learner::WriteLinkedCommunities(std::ostream* out, Float threshold, uint32_t top, const std::string& by,
+                                     uint64_t min_links, uint64_t max_bytes) {
+  Linked r;
+  LinkedCommunities(threshold, top, by, min_links, &r, max_bytes);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.valid + r.skipped << " " << G9(threshold) << " " << by << " "
+       << top << " " << min_links << " " << r.skipped << "\n";
+  for (size_t k = 0; k < r.size.size(); ++k) {
+    uint32_t n = 0;
+    while (n < top && r.partner[k * top + n] >= 0) ++n;
+    *out << k << " " << r.size[k] << " " << r.internal[k] << " " << n;
+    for (uint32_t t = 0; t < n; ++t)
+      *out << " " << r.partner[k * top + t] << " " << r.links[k * top + t] << " " << r.shared[k * top + t];
     *out << "\n";
   }
   return static_cast<bool>(*out);

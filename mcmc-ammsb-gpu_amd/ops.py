@@ -1261,6 +1261,81 @@ class CommunityRelations:
         return self.rl.last_kernel_name()
 
 
+class CommunityLinks:
+    """How the detected communities are linked to each other (include/ammsb_connect.h): node-major membership bits in
+    community order from one streaming pass over pi, the K x K matrix of the links of an edge list between every two
+    communities by walking the two bit rows of every edge, and per community the partners it is linked to most.  Integer
+    counts over binary32 compares and integer compares of rationals: exact, and independent of the kernel form and of how
+    the edge list is cut into calls.  Owns nothing but the tensors it returns."""
+
+    def __init__(self, ctx):
+        from . import _connect
+        self.ctx = ctx
+        self.cn = _connect
+        self.lib = _connect.load()
+
+    def mask(self, pi, thr):
+        """-> the membership bits of (pi, thr): a [N, ceil(K / 64)] int64 device tensor, bit k & 63 of word k >> 6 of row
+        a set iff pi[a, k] >= thr"""
+        thr = self.cn.check_threshold(thr)
+        N, K = int(pi.desc.num_rows), int(pi.cols)
+        if N and not int(self.lib.ammsb_connect_mask_bytes(N, K)):
+            raise AmmsbError("community links: no mask for a %d x %d pi" % (N, K))
+        out = self.ctx.empty((N, (K + 63) // 64), torch.int64)
+        if N:  # (an empty tensor has no address)
+            self.cn.check(self.lib.ammsb_connect_mask(C.byref(pi.desc), thr, _ptr(out), _stream()))
+        return out
+
+    def edges(self, mask, N, K, edges, directed=None, counts=None):
+        """mask: what mask() returned for an N x K pi; edges: keys (a << 32) | b, a host array or a contiguous 1-d int64
+        (uint64 bits) device tensor.  Adds them to directed, a [K, K] int64 (uint64 bits) device tensor, and to counts
+        [2] int64 (valid, skipped); either is made and zeroed where none is given -> (directed, counts)"""
+        edges = _edge_keys(self.ctx, edges, "community links")
+        N, K, n = int(N), int(K), int(edges.numel())
+        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
+            raise AmmsbError("community links: not the mask of a %d x %d pi" % (N, K))
+        directed = self.ctx.zeros((K, K), torch.int64) if directed is None else directed
+        counts = self.ctx.zeros((2,), torch.int64) if counts is None else counts
+        if directed.dtype != torch.int64 or not directed.is_contiguous() or tuple(directed.shape) != (K, K):
+            raise AmmsbError("community links: directed must be a contiguous [K, K] int64 (uint64 bits) device tensor")
+        if counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != 2:
+            raise AmmsbError("community links: counts must be a contiguous [2] int64 device tensor")
+        if n:  # (an empty list is a valid no-op; its empty tensor has no address)
+            self.cn.check(self.lib.ammsb_connect_edges(_ptr(mask), N, K, _ptr(edges), n, _ptr(directed), _ptr(counts),
+                                                       _stream()))
+        return directed, counts
+
+    def finish(self, directed):
+        """-> links [K, K] int64 (uint64 bits) = directed + its transpose"""
+        if directed.dtype != torch.int64 or not directed.is_contiguous() or directed.dim() != 2 or \
+                directed.shape[0] != directed.shape[1] or not directed.numel():
+            raise AmmsbError("community links: directed must be a contiguous [K, K] int64 (uint64 bits) device tensor")
+        links = self.ctx.empty(tuple(directed.shape), torch.int64)
+        self.cn.check(self.lib.ammsb_connect_finish(_ptr(directed), int(directed.shape[0]), _ptr(links), _stream()))
+        return links
+
+    def top(self, links, overlap, by="density", top=4, min_links=1):
+        """links: the finished [K, K] int64 device tensor; overlap: CommunityRelations' finished [K, K] int32 (uint32 bits)
+        -> (partner [K, top] int32, plinks [K, top] int64 (uint64 bits), pshared [K, top] int32 (uint32 bits)) on the
+        device: per community the `top` others with at least max(1, min_links) links to it, ranked by `by` (links or
+        density), equal values by id ascending; -1, 0 and 0 in empty slots"""
+        measure, top, min_links = self.cn.check_args(by, top, min_links)
+        if links.dtype != torch.int64 or not links.is_contiguous() or links.dim() != 2 or \
+                links.shape[0] != links.shape[1] or not links.numel():
+            raise AmmsbError("community links: links must be a contiguous [K, K] int64 (uint64 bits) device tensor")
+        if overlap.dtype != torch.int32 or not overlap.is_contiguous() or tuple(overlap.shape) != tuple(links.shape):
+            raise AmmsbError("community links: overlap must be a contiguous [K, K] int32 (uint32 bits) device tensor")
+        K = int(links.shape[0])
+        partner, pshared = self.ctx.empty((K, top), torch.int32), self.ctx.empty((K, top), torch.int32)
+        plinks = self.ctx.empty((K, top), torch.int64)
+        self.cn.check(self.lib.ammsb_connect_top(_ptr(links), _ptr(overlap), K, measure, top, min_links, _ptr(partner),
+                                                 _ptr(plinks), _ptr(pshared), _stream()))
+        return partner, plinks, pshared
+
+    def kernel_name(self):
+        return self.cn.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

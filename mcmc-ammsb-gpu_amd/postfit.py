@@ -1,6 +1,6 @@
 """The post-fit analyses of a Learner: what reads a fitted model out -- memberships and communities, link prediction,
 link communities, community quality, the three comparisons with a ground-truth cover (F1 match, overlapping NMI, Omega
-index), and how the detected communities relate to each other.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
+index), how the detected communities relate to each other and how they are linked.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
 holds all of pi, so none is a collective), and nothing of the iteration is touched -- no RNG stream, no counter, no
 buffer.  There is no CPU path: without a device every one of them raises."""
 import numpy as np
@@ -361,3 +361,46 @@ class PostFit:
         matrix = overlap.cpu().numpy().view(np.uint32)
         return _relate.Related(threshold, by, min_overlap, np.diagonal(matrix).astype(np.int64), partner.cpu().numpy(),
                                shared.cpu().numpy().view(np.uint32), matrix if dense else None, N=self.cfg.N)
+
+    # ---- how the detected communities are linked to each other (include/ammsb_connect.h)
+    def _connect(self):
+        return self._postfit_op("_community_links_op", "CommunityLinks", "the community links")
+
+    def _community_links(self, threshold, edges):
+        """-> (links [K, K] int64, counts [2] int64) on the device"""
+        cl = self._connect()
+        self.drain()
+        edges = self._linkcomm_edges(edges)
+        N, K = self.cfg.N, self.cfg.K
+        directed, counts = cl.edges(cl.mask(self.pi, threshold), N, K, edges)
+        return cl.finish(directed), counts
+
+    def CommunityLinks(self, threshold=0.05, edges=None):
+        """-> [K, K] int64 device tensor: links[k, l] = directed[k, l] + directed[l, k], directed[k, l] being the keys
+        (a << 32) | b of `edges` (host array or device tensor, either order of the ends, duplicates and a == b as
+        written, a key with an end >= N left out; default: TrainingLinks()) with pi[a, k] >= threshold and pi[b, l] >=
+        threshold.  Symmetric; the diagonal is twice CommunityQuality's internal.  Integer adds: exact."""
+        from . import _connect
+        threshold = _connect.check_threshold(threshold)
+        return self._community_links(threshold, edges)[0]
+
+    def LinkedCommunities(self, threshold=0.05, top=4, by="density", min_links=1, edges=None, max_bytes=1 << 30, dense=False):
+        """-> _connect.Linked: per community k the `top` other communities l with at least max(1, min_links) links of
+        `edges` (as CommunityLinks takes them) between them, ranked by `by` -- "links" (the count w) or "density" (w over
+        the d_k d_l - overlap[k, l] ordered pairs of distinct nodes, overlap from CommunityOverlap(threshold, max_bytes);
+        a pair of communities without such a node pair is no partner) -- as exact rationals, equal values by id
+        ascending: .size, .internal, .partner (-1 in an empty slot), .links, .shared, .valid, .skipped, and in float64 on
+        the host .density and .within; .matrix (the whole CommunityLinks, on the host) with dense=True; .bridged() lists
+        the pairs linked as densely as one of them is inside.  The integers are exact."""
+        from . import _connect
+        threshold = _connect.check_threshold(threshold)
+        _, top, min_links = _connect.check_args(by, top, min_links)
+        overlap = self.CommunityOverlap(threshold, max_bytes)
+        links, counts = self._community_links(threshold, edges)
+        partner, plinks, pshared = self._connect().top(links, overlap, by, top, min_links)
+        matrix = links.cpu().numpy().view(np.uint64)
+        size = np.diagonal(overlap.cpu().numpy().view(np.uint32)).astype(np.int64)
+        valid, skipped = (int(v) for v in counts.cpu().numpy())
+        return _connect.Linked(threshold, by, min_links, size, (np.diagonal(matrix) // np.uint64(2)).astype(np.int64),
+                               partner.cpu().numpy(), plinks.cpu().numpy().view(np.uint64),
+                               pshared.cpu().numpy().view(np.uint32), valid, skipped, matrix if dense else None, N=self.cfg.N)
