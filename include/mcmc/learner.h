@@ -206,6 +206,24 @@ class Learner {
   bool WriteLinkedCommunities(std::ostream* out, Float threshold, uint32_t top, const std::string& by,
                               uint64_t min_links = 1, uint64_t max_bytes = 1ull << 30);
 
+  // Is the cover better than chance?  The overlapping modularity (EQ of Shen et al.) of the cover pi[a, k] >= threshold
+  // against `edges` (keys (a << 32) | b as include/ammsb_modularity.h takes them; nullptr: every training link once),
+  // fewer than 2^31 keys.  internal and volume are the device's 128-bit sums IN and SV in units of 2^-62, exact; Derive()
+  // is the header's float64 statement over them: one conversion that rounds once, ldexp, then q_k = (2 in_k - s_k s_k /
+  // (2m)) / (2m) and q = the sum in index order, -1 when m = 0.  std::invalid_argument on a bad threshold or a list of
+  // 2^31 keys or more.  Waits, reads and perturbs like CommunityQuality.
+  struct ModularityScore {
+    std::vector<unsigned __int128> internal, volume;  // [K]
+    std::vector<uint32_t> degree;                     // [N]
+    uint64_t links = 0, skipped = 0;                  // m, the valid keys; those with an end >= N
+    double q = -1;
+    std::vector<double> q_each, in_each, s_each;      // [K]
+    void Derive();
+  };
+  void Modularity(Float threshold, const std::vector<Edge>* edges, ModularityScore* result);
+  // `# N K E threshold skipped q`, then `k q_k in_k s_k internal volume` per community: %.17g and 32 hexadecimal digits.
+  bool WriteModularity(std::ostream* out, Float threshold, const std::vector<Edge>* edges = nullptr);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

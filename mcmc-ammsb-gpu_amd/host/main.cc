@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy, modularityOut;
   bool haveCoverThreshold = false;
   double coverThreshold = 0.05;
   bool haveRelatedThreshold = false, haveRelatedTop = false;
@@ -87,6 +87,8 @@ int main(int argc, char** argv) {
   double linkedThreshold = 0.05;
   long linkedTop = 4;
   long long linkedMinLinks = 1;
+  bool haveModularityThreshold = false;
+  double modularityThreshold = 0.05;
   bool haveQualityThreshold = false;
   double qualityThreshold = 0.05;
   bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
@@ -238,6 +240,14 @@ int main(int argc, char** argv) {
                in >> linkedMinLinks;
                return !in.fail() && in.eof();
              }},
+      OptStr("modularity-out", 0, &modularityOut),  // (new) after the last perplexity line: `# N K E threshold skipped q`, then `k q_k in_k s_k internal volume` per community: the overlapping modularity of the cover against the training links, the 128-bit sums as 32 hexadecimal digits
+      Option{"modularity-threshold", 0, "0.05 (new, with --modularity-out: a node is a member of k iff pi[a, k] >= it)",
+             [&](const std::string& v) {
+               haveModularityThreshold = true;
+               std::istringstream in(v);
+               in >> modularityThreshold;
+               return !in.fail() && in.eof();
+             }},
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -346,6 +356,9 @@ int main(int argc, char** argv) {
   if (!(linkedThreshold >= 0) || !std::isfinite(static_cast<float>(linkedThreshold)))
     Fatal("--linked-communities-threshold must be finite and >= 0");
   if (linkedMinLinks < 0) Fatal("--linked-communities-min-links must be >= 0");
+  if (haveModularityThreshold && modularityOut.empty()) Fatal("--modularity-threshold needs --modularity-out FILE");
+  if (!(modularityThreshold >= 0) || !std::isfinite(static_cast<float>(modularityThreshold)))
+    Fatal("--modularity-threshold must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -572,6 +585,18 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("linked communities: ") + e.what());
+    }
+  }
+  if (!modularityOut.empty()) {
+    // every rank holds all of pi and the training links: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(modularityOut);
+        if (!out.good() || !learner.WriteModularity(&out, static_cast<mcmc::Float>(modularityThreshold)))
+          Fatal("cannot write modularity " + modularityOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("modularity: ") + e.what());
     }
   }
   learner.PrintStats();

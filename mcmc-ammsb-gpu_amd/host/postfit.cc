@@ -1,7 +1,8 @@
 // mcmc::Learner's post-fit analyses (include/mcmc/learner.h): what reads a fitted model out -- memberships and
 // communities, link prediction, link communities, community quality, the three comparisons with a ground-truth cover
-// (F1 match, overlapping NMI, Omega index), how the detected communities relate to each other and how they are linked.  Each is
-// a thin driver of one library of its own (libammsb_readout.so ... libammsb_connect.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
+// (F1 match, overlapping NMI, Omega index), how the detected communities relate to each other, how they are linked and the
+// overlapping modularity of the cover.  Each is
+// a thin driver of one library of its own (libammsb_readout.so ... libammsb_modularity.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
 // read the results back, and for the Write* methods print them.  Nothing here touches the training loop of learner.cc.
 #include "mcmc/learner.h"
 #include "ammsb_readout.h"
@@ -13,6 +14,7 @@
 #include "ammsb_omega.h"
 #include "ammsb_relate.h"
 #include "ammsb_connect.h"
+#include "ammsb_modularity.h"
 
 #include <hip/hip_runtime.h>
 
@@ -876,6 +878,99 @@ bool Learner::WriteLinkedCommunities(std::ostream* out, Float threshold, uint32_
       *out << " " << r.partner[k * top + t] << " " << r.links[k * top + t] << " " << r.shared[k * top + t];
     *out << "\n";
   }
+  return static_cast<bool>(*out);
+}
+
+// ---- is the cover better than chance: libammsb_modularity.so over libammsb_connect.so's mask of pi and an edge list
+void Learner::ModularityScore::Derive() {
+#pragma STDC FP_CONTRACT OFF
+  const size_t K = internal.size();
+  in_each.resize(K);
+  s_each.resize(K);
+  q_each.assign(K, -1.0);
+  q = -1.0;
+  for (size_t k = 0; k < K; ++k) {
+    // (the conversion of a 128-bit integer rounds once, to nearest even; the scaling is exact)
+    in_each[k] = std::ldexp(static_cast<double>(internal[k]), -static_cast<int>(AMMSB_MODULARITY_FRAC_BITS));
+    s_each[k] = std::ldexp(static_cast<double>(volume[k]), -static_cast<int>(AMMSB_MODULARITY_FRAC_BITS));
+  }
+  if (links == 0) return;
+  const double two_m = static_cast<double>(2 * links);
+  q = 0.0;
+  for (size_t k = 0; k < K; ++k) {
+    const double twice = 2.0 * in_each[k];
+    const double square = s_each[k] * s_each[k];
+    const double chance = square / two_m;
+    const double diff = twice - chance;
+    q_each[k] = diff / two_m;
+    q += q_each[k];
+  }
+}
+
+void Learner::Modularity(Float threshold, const std::vector<Edge>* edges, ModularityScore* result) {
+  CheckThreshold("Modularity", threshold);
+  if (edges && edges->size() >= AMMSB_MODULARITY_MAX_EDGES)
+    throw std::invalid_argument("Modularity: an edge list of 2^31 keys or more");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  if (K == 0 || K > AMMSB_MODULARITY_MAX_COLS) throw std::runtime_error("Modularity: K outside 1..8192");
+  std::vector<Edge> training;
+  if (!edges) {
+    training = SortedTrainingLinks(cfg_);
+    if (training.size() >= AMMSB_MODULARITY_MAX_EDGES) throw std::invalid_argument("Modularity: 2^31 training links or more");
+    edges = &training;
+  }
+  result->internal.assign(K, 0);
+  result->volume.assign(K, 0);
+  result->degree.assign(N, 0);
+  result->links = 0;
+  result->skipped = edges->size();  // (without a node every key has an end >= N)
+  if (!edges->empty() && N > 0) {
+    hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
+    const clcuda::Context context = queue_.GetContext();
+    const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
+    clcuda::Buffer<uint64_t> d_mask(context, words), d_sums(context, 4 * K + 2);  // internal, volume, counts
+    clcuda::Buffer<uint32_t> d_degree(context, N);
+    clcuda::Buffer<Edge> d_edges(context, queue_, edges->begin(), edges->end());
+    hipError_t e = hipMemsetAsync(d_sums(), 0, (4 * K + 2) * sizeof(uint64_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_degree(), 0, N * sizeof(uint32_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("Modularity: memset: ") + hipGetErrorString(e));
+    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
+    rc = ammsb_modularity_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), edges->size(), d_degree(), d_sums(),
+                                d_sums() + 4 * K, stream);
+    if (rc == AMMSB_OK)
+      rc = ammsb_modularity_nodes(d_mask(), N, static_cast<uint32_t>(K), d_degree(), d_sums() + 2 * K, stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_modularity", rc, ammsb_modularity_last_error());
+    std::vector<uint64_t> sums(4 * K + 2);
+    d_sums.Read(queue_, 4 * K + 2, sums.data());
+    d_degree.Read(queue_, N, result->degree.data());
+    queue_.Finish();
+    typedef unsigned __int128 u128;
+    for (uint64_t k = 0; k < K; ++k) {
+      result->internal[k] = (static_cast<u128>(sums[2 * k + 1]) << 64) | sums[2 * k];
+      result->volume[k] = (static_cast<u128>(sums[2 * K + 2 * k + 1]) << 64) | sums[2 * K + 2 * k];
+    }
+    result->links = sums[4 * K];
+    result->skipped = sums[4 * K + 1];
+  }
+  result->Derive();
+}
+
+bool Learner::WriteModularity(std::ostream* out, Float threshold, const std::vector<Edge>* edges) {
+  ModularityScore r;
+  Modularity(threshold, edges, &r);
+  const auto hex = [](unsigned __int128 v) {
+    char buf[40];
+    snprintf(buf, sizeof(buf), "%016llx%016llx", static_cast<unsigned long long>(v >> 64), static_cast<unsigned long long>(v));
+    return std::string(buf);
+  };
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.links + r.skipped << " " << G9(threshold) << " " << r.skipped
+       << " " << G17(r.q) << "\n";
+  for (size_t k = 0; k < r.q_each.size(); ++k)
+    *out << k << " " << G17(r.q_each[k]) << " " << G17(r.in_each[k]) << " " << G17(r.s_each[k]) << " " << hex(r.internal[k])
+         << " " << hex(r.volume[k]) << "\n";
   return static_cast<bool>(*out);
 }
 

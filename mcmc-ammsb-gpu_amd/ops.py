@@ -1336,6 +1336,69 @@ class CommunityLinks:
         return self.cn.last_kernel_name()
 
 
+class Modularity:
+    """The overlapping modularity of the detected cover (include/ammsb_modularity.h): over CommunityLinks' node-major
+    membership bits, an edge pass that adds floor(2^62 / (O_a O_b)) per community that holds both ends of an edge and
+    counts the degrees, and a node pass that adds deg[a] floor(2^62 / O_a) per membership, both into 128-bit integers
+    (two int64 words each, uint64 bits: low, high).  Integer adds: exact, and independent of the kernel form and of how
+    the edge list is cut into calls.  Owns nothing but the tensors it returns."""
+
+    def __init__(self, ctx):
+        from . import _modularity
+        self.ctx = ctx
+        self.md = _modularity
+        self.lib = _modularity.load()
+        self.links = CommunityLinks(ctx)
+
+    def _mask(self, mask, N, K):
+        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
+            raise AmmsbError("modularity: not the mask of a %d x %d pi" % (N, K))
+
+    def edges(self, mask, N, K, edges, state=None):
+        """mask: what CommunityLinks.mask() returned for an N x K pi; edges: keys (a << 32) | b, a host array or a
+        contiguous 1-d int64 (uint64 bits) device tensor, fewer than 2^31.  Adds them to state = (degree [N] int32 (uint32
+        bits), internal [2 K] int64, counts [2] int64 (valid, skipped)), which is made and zeroed where none is given
+        -> state"""
+        edges = _edge_keys(self.ctx, edges, "modularity")
+        N, K, n = int(N), int(K), self.md.check_keys(edges.numel())
+        self._mask(mask, N, K)
+        if state is None:
+            state = (self.ctx.zeros((N,), torch.int32), self.ctx.zeros((2 * K,), torch.int64), self.ctx.zeros((2,), torch.int64))
+        degree, internal, counts = state
+        if degree.dtype != torch.int32 or not degree.is_contiguous() or degree.numel() != N:
+            raise AmmsbError("modularity: degree must be a contiguous [N] int32 (uint32 bits) device tensor")
+        if internal.dtype != torch.int64 or not internal.is_contiguous() or internal.numel() != 2 * K:
+            raise AmmsbError("modularity: internal must be a contiguous [2 K] int64 (uint64 bits) device tensor")
+        if counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != 2:
+            raise AmmsbError("modularity: counts must be a contiguous [2] int64 device tensor")
+        if n:  # (an empty list is a valid no-op; its empty tensor has no address)
+            self.md.check(self.lib.ammsb_modularity_edges(_ptr(mask), N, K, _ptr(edges), n, _ptr(degree), _ptr(internal),
+                                                          _ptr(counts), _stream()))
+        return state
+
+    def nodes(self, mask, N, K, degree):
+        """after the last edges(): -> volume [2 K] int64 (uint64 bits)"""
+        N, K = int(N), int(K)
+        self._mask(mask, N, K)
+        if degree.dtype != torch.int32 or not degree.is_contiguous() or degree.numel() != N:
+            raise AmmsbError("modularity: degree must be a contiguous [N] int32 (uint32 bits) device tensor")
+        volume = self.ctx.zeros((2 * K,), torch.int64)
+        if N:
+            self.md.check(self.lib.ammsb_modularity_nodes(_ptr(mask), N, K, _ptr(degree), _ptr(volume), _stream()))
+        return volume
+
+    def run(self, pi, thr, edges):
+        """-> (internal [2 K], volume [2 K], counts [2], degree [N]) device tensors for the cover (pi, thr) and the edge
+        list"""
+        N, K = int(pi.desc.num_rows), int(pi.cols)
+        mask = self.links.mask(pi, self.md.check_threshold(thr))
+        degree, internal, counts = self.edges(mask, N, K, edges)
+        return internal, self.nodes(mask, N, K, degree), counts, degree
+
+    def kernel_name(self):
+        return self.md.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

@@ -1,6 +1,6 @@
 """The post-fit analyses of a Learner: what reads a fitted model out -- memberships and communities, link prediction,
 link communities, community quality, the three comparisons with a ground-truth cover (F1 match, overlapping NMI, Omega
-index), how the detected communities relate to each other and how they are linked.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
+index), how the detected communities relate to each other, how they are linked and the overlapping modularity of the cover.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
 holds all of pi, so none is a collective), and nothing of the iteration is touched -- no RNG stream, no counter, no
 buffer.  There is no CPU path: without a device every one of them raises."""
 import numpy as np
@@ -404,3 +404,26 @@ class PostFit:
         return _connect.Linked(threshold, by, min_links, size, (np.diagonal(matrix) // np.uint64(2)).astype(np.int64),
                                partner.cpu().numpy(), plinks.cpu().numpy().view(np.uint64),
                                pshared.cpu().numpy().view(np.uint32), valid, skipped, matrix if dense else None, N=self.cfg.N)
+
+    # ---- is the cover better than chance? (include/ammsb_modularity.h)
+    def _modularity(self):
+        return self._postfit_op("_modularity_op", "Modularity", "the modularity")
+
+    def Modularity(self, threshold=0.05, edges=None, degree=False):
+        """-> _modularity.Modularity: the overlapping modularity (EQ of Shen et al.) of the cover pi[a, k] >= threshold
+        against `edges` (host array or device tensor of (a << 32) | b, either order of the ends, duplicates and a == b as
+        written, a key with an end >= N left out; default: TrainingLinks()), fewer than 2^31 keys: .q and .q_each [K] in
+        float64, derived on the host from .internal and .volume, the device's 128-bit sums of floor(2^62 / (O_a O_b)) over
+        the links inside k and of deg[a] floor(2^62 / O_a) over the members of k, as Python ints; .in_each, .s_each,
+        .links, .skipped, and .degree [N] uint32 with degree=True.  The integers are exact and the same from run to
+        run."""
+        from . import _modularity
+        threshold = _modularity.check_threshold(threshold)
+        md = self._modularity()
+        self.drain()
+        edges = self._linkcomm_edges(edges)
+        _modularity.check_keys(edges.numel())
+        internal, volume, counts, deg = md.run(self.pi, threshold, edges)
+        valid, skipped = (int(v) for v in counts.cpu().numpy())
+        return _modularity.Modularity(threshold, _modularity.wide(internal.cpu().numpy()), _modularity.wide(volume.cpu().numpy()),
+                                      valid, skipped, deg.cpu().numpy().view(np.uint32) if degree else None, N=self.cfg.N)
