@@ -224,6 +224,31 @@ class Learner {
   // `# N K E threshold skipped q`, then `k q_k in_k s_k internal volume` per community: %.17g and 32 hexadecimal digits.
   bool WriteModularity(std::ostream* out, Float threshold, const std::vector<Edge>* edges = nullptr);
 
+  // How does a single node sit in the cover?  Per node of an adjacency (nullptr: the training graph's rows; else both
+  // directions of every key (a << 32) | b of `edges`, a key with an end >= N counted in skipped) the integers of
+  // include/ammsb_roles.h for the cover pi[a, k] >= threshold: with c[a, k] the neighbours of a in k, degree, own,
+  // embedded, reached, votes, squares, the `top` (1..16) communities with the largest c (among "all": every k with c >=
+  // max(1, min_count); "own": a's communities with c >= min_count) and per community ksum, ksq, kmembers, all exact.
+  // Derive() is the header's float64 statement over them.  std::invalid_argument on a bad threshold, top or among, or a
+  // row of more than 2^25 targets.  Waits, reads and perturbs like CommunityQuality.
+  struct NodeRolesResult {
+    uint32_t top = 0;
+    std::vector<uint32_t> degree, own, embedded, reached, hflags;  // [N]
+    std::vector<uint64_t> votes, squares;                          // [N]
+    std::vector<int32_t> home;                                     // [N, top], -1: empty
+    std::vector<uint32_t> hcount;                                  // [N, top]
+    std::vector<uint64_t> ksum, ksq, kmembers;                     // [K]
+    uint64_t valid = 0, skipped = 0;                               // targets counted; targets or keys with an end >= N
+    std::vector<double> embeddedness, participation, z;            // [N], [N], [N, top]
+    void Derive();
+  };
+  void NodeRoles(Float threshold, const std::vector<Edge>* edges, uint32_t top, const std::string& among, uint32_t min_count,
+                 NodeRolesResult* result);
+  // `# N K M threshold among top min_count skipped`, `c k members ksum ksq` per community, `n a degree own embedded reached
+  // votes squares nslots k0 c0 f0 ...` per node: integers throughout.
+  bool WriteNodeRoles(std::ostream* out, Float threshold, uint32_t top = 4, const std::string& among = "all",
+                      uint32_t min_count = 0, const std::vector<Edge>* edges = nullptr);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

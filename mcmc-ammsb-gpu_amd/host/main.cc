@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy, modularityOut;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy, modularityOut, rolesOut, rolesAmong = "all";
   bool haveCoverThreshold = false;
   double coverThreshold = 0.05;
   bool haveRelatedThreshold = false, haveRelatedTop = false;
@@ -89,6 +89,9 @@ int main(int argc, char** argv) {
   long long linkedMinLinks = 1;
   bool haveModularityThreshold = false;
   double modularityThreshold = 0.05;
+  bool haveRolesThreshold = false, haveRolesTop = false, haveRolesAmong = false;
+  double rolesThreshold = 0.05;
+  long rolesTop = 4;
   bool haveQualityThreshold = false;
   double qualityThreshold = 0.05;
   bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
@@ -248,6 +251,27 @@ int main(int argc, char** argv) {
                in >> modularityThreshold;
                return !in.fail() && in.eof();
              }},
+      OptStr("node-roles-out", 0, &rolesOut),  // (new) after the last perplexity line: `# N K M threshold among top min_count skipped`, `c k members ksum ksq` per community, `n a degree own embedded reached votes squares nslots k0 c0 f0 ...` per node: how each node sits in the cover against the training adjacency
+      Option{"node-roles-threshold", 0, "0.05 (new, with --node-roles-out: a node is a member of k iff pi[a, k] >= it)",
+             [&](const std::string& v) {
+               haveRolesThreshold = true;
+               std::istringstream in(v);
+               in >> rolesThreshold;
+               return !in.fail() && in.eof();
+             }},
+      Option{"node-roles-top", 0, "4 (new, with --node-roles-out: communities kept per node, 1..16)",
+             [&](const std::string& v) {
+               haveRolesTop = true;
+               std::istringstream in(v);
+               in >> rolesTop;
+               return !in.fail() && in.eof();
+             }},
+      Option{"node-roles-among", 0, "all (new, with --node-roles-out: all = every community a neighbour is in, own = the node's own)",
+             [&](const std::string& v) {
+               haveRolesAmong = true;
+               rolesAmong = v;
+               return true;
+             }},
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -359,6 +383,12 @@ int main(int argc, char** argv) {
   if (haveModularityThreshold && modularityOut.empty()) Fatal("--modularity-threshold needs --modularity-out FILE");
   if (!(modularityThreshold >= 0) || !std::isfinite(static_cast<float>(modularityThreshold)))
     Fatal("--modularity-threshold must be finite and >= 0");
+  if ((haveRolesThreshold || haveRolesTop || haveRolesAmong) && rolesOut.empty())
+    Fatal("--node-roles-threshold / --node-roles-top / --node-roles-among need --node-roles-out FILE");
+  if (!(rolesThreshold >= 0) || !std::isfinite(static_cast<float>(rolesThreshold)))
+    Fatal("--node-roles-threshold must be finite and >= 0");
+  if (rolesTop < 1 || rolesTop > 16) Fatal("--node-roles-top must be in 1..16");
+  if (rolesAmong != "all" && rolesAmong != "own") Fatal("--node-roles-among must be all or own");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -597,6 +627,19 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("modularity: ") + e.what());
+    }
+  }
+  if (!rolesOut.empty()) {
+    // every rank holds all of pi and the training adjacency: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(rolesOut);
+        if (!out.good() || !learner.WriteNodeRoles(&out, static_cast<mcmc::Float>(rolesThreshold),
+                                                   static_cast<uint32_t>(rolesTop), rolesAmong))
+          Fatal("cannot write node roles " + rolesOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("node roles: ") + e.what());
     }
   }
   learner.PrintStats();

@@ -1,8 +1,8 @@
 // mcmc::Learner's post-fit analyses (include/mcmc/learner.h): what reads a fitted model out -- memberships and
 // communities, link prediction, link communities, community quality, the three comparisons with a ground-truth cover
-// (F1 match, overlapping NMI, Omega index), how the detected communities relate to each other, how they are linked and the
-// overlapping modularity of the cover.  Each is
-// a thin driver of one library of its own (libammsb_readout.so ... libammsb_modularity.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
+// (F1 match, overlapping NMI, Omega index), how the detected communities relate to each other, how they are linked, the
+// overlapping modularity of the cover and the role of every node in it.  Each is
+// a thin driver of one library of its own (libammsb_readout.so ... libammsb_roles.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
 // read the results back, and for the Write* methods print them.  Nothing here touches the training loop of learner.cc.
 #include "mcmc/learner.h"
 #include "ammsb_readout.h"
@@ -15,6 +15,7 @@
 #include "ammsb_relate.h"
 #include "ammsb_connect.h"
 #include "ammsb_modularity.h"
+#include "ammsb_roles.h"
 
 #include <hip/hip_runtime.h>
 
@@ -971,6 +972,160 @@ bool Learner::WriteModularity(std::ostream* out, Float threshold, const std::vec
   for (size_t k = 0; k < r.q_each.size(); ++k)
     *out << k << " " << G17(r.q_each[k]) << " " << G17(r.in_each[k]) << " " << G17(r.s_each[k]) << " " << hex(r.internal[k])
          << " " << hex(r.volume[k]) << "\n";
+  return static_cast<bool>(*out);
+}
+
+// ---- how does a single node sit in the cover: libammsb_roles.so over libammsb_connect.so's mask of pi and a CSR adjacency
+void Learner::NodeRolesResult::Derive() {
+#pragma STDC FP_CONTRACT OFF
+  const size_t n = degree.size(), K = ksum.size();
+  embeddedness.assign(n, -1.0);
+  participation.assign(n, -1.0);
+  z.assign(n * top, 0.0);
+  // (every integer is converted once, to nearest even)
+  std::vector<double> mean(K, 0.0), sigma(K, 0.0);  // sigma 0: no z in this community
+  for (size_t k = 0; k < K; ++k) {
+    if (kmembers[k] < 2) continue;
+    const double members = static_cast<double>(kmembers[k]);
+    mean[k] = static_cast<double>(ksum[k]) / members;
+    const double second = static_cast<double>(ksq[k]) / members;
+    const double square = mean[k] * mean[k];
+    const double var = second - square;
+    if (var > 0) sigma[k] = std::sqrt(var);
+  }
+  for (size_t i = 0; i < n; ++i) {
+    if (degree[i] > 0) embeddedness[i] = static_cast<double>(embedded[i]) / static_cast<double>(degree[i]);
+    if (votes[i] > 0) {
+      const double v = static_cast<double>(votes[i]);
+      const double vv = v * v;
+      const double ratio = static_cast<double>(squares[i]) / vv;
+      participation[i] = 1.0 - ratio;
+    }
+    for (uint32_t j = 0; j < top; ++j) {
+      const int32_t k = home[i * top + j];
+      if (k < 0 || !(sigma[k] > 0)) continue;
+      const double diff = static_cast<double>(hcount[i * top + j]) - mean[k];
+      z[i * top + j] = diff / sigma[k];
+    }
+  }
+}
+
+void Learner::NodeRoles(Float threshold, const std::vector<Edge>* edges, uint32_t top, const std::string& among,
+                        uint32_t min_count, NodeRolesResult* result) {
+  CheckThreshold("NodeRoles", threshold);
+  if (top == 0 || top > AMMSB_ROLES_MAX_TOP) throw std::invalid_argument("NodeRoles: top must be in 1..16");
+  if (among != "all" && among != "own") throw std::invalid_argument("NodeRoles: among must be \"all\" or \"own\"");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  if (K == 0 || K > AMMSB_ROLES_MAX_COLS) throw std::runtime_error("NodeRoles: K outside 1..8192");
+  // the adjacency: the training graph's rows, or both directions of every valid key of the list, in the list's order
+  std::vector<uint64_t> offsets;
+  std::vector<Vertex> targets;
+  uint64_t lost = 0;  // keys with an end >= N
+  if (!edges) {
+    cfg_.trainingGraph->ExportCSR(&offsets, &targets);
+  } else {
+    offsets.assign(N + 1, 0);
+    for (Edge e : *edges) {
+      const uint64_t a = e >> 32, b = e & 0xFFFFFFFFull;
+      if (a >= N || b >= N) {
+        ++lost;
+        continue;
+      }
+      ++offsets[a + 1];
+      ++offsets[b + 1];
+    }
+    for (uint64_t a = 0; a < N; ++a) offsets[a + 1] += offsets[a];
+    targets.resize(offsets[N]);
+    std::vector<uint64_t> at(offsets.begin(), offsets.end() - 1);
+    for (Edge e : *edges) {
+      const uint64_t a = e >> 32, b = e & 0xFFFFFFFFull;
+      if (a >= N || b >= N) continue;
+      targets[at[a]++] = static_cast<Vertex>(b);
+      targets[at[b]++] = static_cast<Vertex>(a);
+    }
+  }
+  if (offsets.size() != N + 1) throw std::runtime_error("NodeRoles: the adjacency does not have N rows");
+  for (uint64_t a = 0; a < N; ++a)
+    if (offsets[a + 1] - offsets[a] > AMMSB_ROLES_MAX_ROW) throw std::invalid_argument("NodeRoles: a row of more than 2^25 targets");
+  NodeRolesResult& r = *result;
+  r.top = top;
+  r.degree.assign(N, 0);
+  r.own.assign(N, 0);
+  r.embedded.assign(N, 0);
+  r.reached.assign(N, 0);
+  r.votes.assign(N, 0);
+  r.squares.assign(N, 0);
+  r.home.assign(N * top, -1);
+  r.hcount.assign(N * top, 0);
+  r.hflags.assign(N, 0);
+  r.ksum.assign(K, 0);
+  r.ksq.assign(K, 0);
+  r.kmembers.assign(K, 0);
+  r.valid = 0;
+  r.skipped = lost;
+  if (N > 0) {
+    hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
+    const clcuda::Context context = queue_.GetContext();
+    const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
+    if (targets.empty()) targets.push_back(0);  // (a buffer needs a byte; no offset reaches it)
+    clcuda::Buffer<uint64_t> d_mask(context, words), d_sums(context, 3 * K + 2), d_wide(context, 2 * N);  // ksum ksq kmembers counts; votes squares
+    clcuda::Buffer<uint32_t> d_node(context, 5 * N), d_slots(context, 2 * N * top);  // degree own embedded reached hflags; home hcount
+    clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
+    clcuda::Buffer<Vertex> d_targets(context, queue_, targets.begin(), targets.end());
+    const hipError_t e = hipMemsetAsync(d_sums(), 0, (3 * K + 2) * sizeof(uint64_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("NodeRoles: memset: ") + hipGetErrorString(e));
+    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
+    rc = ammsb_roles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N,
+                           among == "own" ? AMMSB_ROLES_OWN : AMMSB_ROLES_ALL, top, min_count, d_node(), d_node() + N,
+                           d_node() + 2 * N, d_node() + 3 * N, d_wide(), d_wide() + N, reinterpret_cast<int32_t*>(d_slots()),
+                           d_slots() + N * top, d_node() + 4 * N, d_sums(), d_sums() + K, d_sums() + 2 * K, d_sums() + 3 * K,
+                           stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_roles_nodes", rc, ammsb_roles_last_error());
+    std::vector<uint64_t> sums(3 * K + 2), wide(2 * N);
+    std::vector<uint32_t> node(5 * N), slots(2 * N * top);
+    d_sums.Read(queue_, 3 * K + 2, sums.data());
+    d_wide.Read(queue_, 2 * N, wide.data());
+    d_node.Read(queue_, 5 * N, node.data());
+    d_slots.Read(queue_, 2 * N * top, slots.data());
+    queue_.Finish();
+    r.degree.assign(node.begin(), node.begin() + N);
+    r.own.assign(node.begin() + N, node.begin() + 2 * N);
+    r.embedded.assign(node.begin() + 2 * N, node.begin() + 3 * N);
+    r.reached.assign(node.begin() + 3 * N, node.begin() + 4 * N);
+    r.hflags.assign(node.begin() + 4 * N, node.end());
+    r.votes.assign(wide.begin(), wide.begin() + N);
+    r.squares.assign(wide.begin() + N, wide.end());
+    for (uint64_t i = 0; i < N * top; ++i) r.home[i] = static_cast<int32_t>(slots[i]);
+    r.hcount.assign(slots.begin() + N * top, slots.end());
+    r.ksum.assign(sums.begin(), sums.begin() + K);
+    r.ksq.assign(sums.begin() + K, sums.begin() + 2 * K);
+    r.kmembers.assign(sums.begin() + 2 * K, sums.begin() + 3 * K);
+    r.valid = sums[3 * K];
+    r.skipped = lost + sums[3 * K + 1];
+  }
+  r.Derive();
+}
+
+bool Learner::WriteNodeRoles(std::ostream* out, Float threshold, uint32_t top, const std::string& among, uint32_t min_count,
+                             const std::vector<Edge>* edges) {
+  NodeRolesResult r;
+  NodeRoles(threshold, edges, top, among, min_count, &r);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.valid + r.skipped << " " << G9(threshold) << " " << among << " "
+       << top << " " << min_count << " " << r.skipped << "\n";
+  for (size_t k = 0; k < r.ksum.size(); ++k)
+    *out << "c " << k << " " << r.kmembers[k] << " " << r.ksum[k] << " " << r.ksq[k] << "\n";
+  for (size_t a = 0; a < r.degree.size(); ++a) {
+    uint32_t filled = 0;
+    while (filled < top && r.home[a * top + filled] >= 0) ++filled;
+    *out << "n " << a << " " << r.degree[a] << " " << r.own[a] << " " << r.embedded[a] << " " << r.reached[a] << " " << r.votes[a]
+         << " " << r.squares[a] << " " << filled;
+    for (uint32_t j = 0; j < filled; ++j)
+      *out << " " << r.home[a * top + j] << " " << r.hcount[a * top + j] << " " << ((r.hflags[a] >> j) & 1u);
+    *out << "\n";
+  }
   return static_cast<bool>(*out);
 }
 

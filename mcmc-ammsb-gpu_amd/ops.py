@@ -1399,6 +1399,83 @@ class Modularity:
         return self.md.last_kernel_name()
 
 
+class NodeRoles:
+    """How a single node sits in the detected cover (include/ammsb_roles.h): over CommunityLinks' node-major membership
+    bits and a CSR adjacency, a wave per node counts the node's neighbours per community in LDS and reduces them to the
+    node's degree, embedded, reached, votes, squares and top slots, and to the per-community sums ksum, ksq, kmembers.
+    Integer adds and compares: exact, and independent of the kernel form and of how the node range is cut into calls.
+    Owns nothing but the tensors it returns."""
+
+    PER_NODE = (("degree", torch.int32), ("own", torch.int32), ("embedded", torch.int32), ("reached", torch.int32),
+                ("votes", torch.int64), ("squares", torch.int64))
+    PER_COMMUNITY = ("ksum", "ksq", "kmembers")
+
+    def __init__(self, ctx):
+        from . import _roles
+        self.ctx = ctx
+        self.rl = _roles
+        self.lib = _roles.load()
+        self.links = CommunityLinks(ctx)
+
+    def state(self, N, K, top):
+        """-> the zeroed outputs of nodes() for an N x K pi: name -> device tensor (uint32 as int32, uint64 as int64);
+        degree, own, embedded, reached, votes, squares [N]; home, hcount [N, top] and hflags [N] where top > 0; ksum, ksq,
+        kmembers [K]; counts [2] (valid, skipped)"""
+        out = {name: self.ctx.zeros((N,), dtype) for name, dtype in self.PER_NODE}
+        if top:
+            out["home"], out["hcount"] = self.ctx.zeros((N, top), torch.int32), self.ctx.zeros((N, top), torch.int32)
+            out["hflags"] = self.ctx.zeros((N,), torch.int32)
+        for name in self.PER_COMMUNITY:
+            out[name] = self.ctx.zeros((K,), torch.int64)
+        out["counts"] = self.ctx.zeros((2,), torch.int64)
+        return out
+
+    def nodes(self, mask, N, K, offsets, targets, first=0, count=None, among="all", top=4, min_count=0, state=None):
+        """mask: what CommunityLinks.mask() returned for an N x K pi; offsets [N + 1] int64 (uint64 bits) and targets int32
+        (uint32 bits): contiguous device tensors, the CSR of the header.  Handles the nodes first .. first + count - 1
+        (default: through N - 1) into `state`, which is made and zeroed where none is given; calls over disjoint ranges
+        fill one state.  top = 0 skips the selection -> state"""
+        N, K, top = int(N), int(K), int(top)
+        first, count = self.rl.check_nodes((first, N - int(first) if count is None else count), N)
+        code, min_count = self.rl.check_among(among), self.rl.check_min_count(min_count)
+        if top:
+            self.rl.check_top(top)
+        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
+            raise AmmsbError("node roles: not the mask of a %d x %d pi" % (N, K))
+        if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() != N + 1:
+            raise AmmsbError("node roles: offsets must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
+        if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 1:
+            raise AmmsbError("node roles: targets must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        if state is None:
+            state = self.state(N, K, top)
+        for name, dtype in self.PER_NODE + ((("home", torch.int32), ("hcount", torch.int32), ("hflags", torch.int32)) if top else ()):
+            t = state[name]
+            if t.dtype != dtype or not t.is_contiguous() or t.numel() != N * (top if name in ("home", "hcount") else 1):
+                raise AmmsbError("node roles: %s of the state does not fit N = %d, top = %d" % (name, N, top))
+        for name in self.PER_COMMUNITY + ("counts",):
+            t = state[name]
+            if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != (2 if name == "counts" else K):
+                raise AmmsbError("node roles: %s of the state does not fit K = %d" % (name, K))
+        if count:  # (an empty range is a valid no-op; an empty tensor has no address)
+            slot = [_ptr(state[n]) if top else None for n in ("home", "hcount", "hflags")]
+            # an adjacency without a target still needs an address for `targets`: the offsets are read, no target is
+            tgt = targets if targets.numel() else self.ctx.zeros((1,), torch.int32)
+            self.rl.check(self.lib.ammsb_roles_nodes(
+                _ptr(mask), N, K, _ptr(offsets), _ptr(tgt), first, count, code, top, min_count, _ptr(state["degree"]),
+                _ptr(state["own"]), _ptr(state["embedded"]), _ptr(state["reached"]), _ptr(state["votes"]),
+                _ptr(state["squares"]), slot[0], slot[1], slot[2], _ptr(state["ksum"]), _ptr(state["ksq"]),
+                _ptr(state["kmembers"]), _ptr(state["counts"]), _stream()))
+        return state
+
+    def run(self, pi, thr, offsets, targets, **how):
+        """-> the state of nodes() for the cover (pi, thr) and the CSR"""
+        N, K = int(pi.desc.num_rows), int(pi.cols)
+        return self.nodes(self.links.mask(pi, self.rl.check_threshold(thr)), N, K, offsets, targets, **how)
+
+    def kernel_name(self):
+        return self.rl.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

@@ -1,6 +1,6 @@
 """The post-fit analyses of a Learner: what reads a fitted model out -- memberships and communities, link prediction,
 link communities, community quality, the three comparisons with a ground-truth cover (F1 match, overlapping NMI, Omega
-index), how the detected communities relate to each other, how they are linked and the overlapping modularity of the cover.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
+index), how the detected communities relate to each other, how they are linked, the overlapping modularity of the cover and the role of every node in it.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
 holds all of pi, so none is a collective), and nothing of the iteration is touched -- no RNG stream, no counter, no
 buffer.  There is no CPU path: without a device every one of them raises."""
 import numpy as np
@@ -427,3 +427,66 @@ class PostFit:
         valid, skipped = (int(v) for v in counts.cpu().numpy())
         return _modularity.Modularity(threshold, _modularity.wide(internal.cpu().numpy()), _modularity.wide(volume.cpu().numpy()),
                                       valid, skipped, deg.cpu().numpy().view(np.uint32) if degree else None, N=self.cfg.N)
+
+    # ---- how does a single node sit in the cover? (include/ammsb_roles.h)
+    def _roles(self):
+        return self._postfit_op("_roles_op", "NodeRoles", "the node roles")
+
+    def _training_adjacency(self):
+        """-> (offsets [N + 1] int64, targets int32) device tensors: the data set's training adjacency, uploaded on first
+        use and kept"""
+        from . import _roles
+        if getattr(self, "_training_csr_dev", None) is None:
+            off, tgt = self.dataset.training_csr()
+            _roles.check_rows(np.diff(off.astype(np.int64)).max() if off.size > 1 else 0)
+            self._training_csr_dev = (self.ctx.from_numpy(off), self.ctx.from_numpy(tgt))
+        return self._training_csr_dev
+
+    def _symmetric_csr(self, edges):
+        """keys (a << 32) | b -> (offsets, targets, keys with an end >= N): each valid key puts b in a's row and a in b's
+        row (a key a == a puts a twice in a's row), in the order of the list, built on the device"""
+        from . import _roles
+        N = self.cfg.N
+        keys = self._linkcomm_edges(edges)
+        if keys.dtype != torch.int64 or keys.dim() != 1:
+            raise AmmsbError("node roles: edges must be 1-d uint64 keys (a << 32) | b")
+        a, b = (keys >> 32) & 0xFFFFFFFF, keys & 0xFFFFFFFF
+        ok = (a < N) & (b < N)
+        a, b = a[ok], b[ok]
+        src, dst = torch.cat((a, b)), torch.cat((b, a))
+        order = torch.sort(src, stable=True).indices
+        rows = torch.bincount(src, minlength=N)
+        _roles.check_rows(int(rows.max()) if N else 0)
+        offsets = torch.zeros(N + 1, dtype=torch.int64, device=keys.device)
+        offsets[1:] = torch.cumsum(rows, 0)
+        return offsets, dst[order].to(torch.int32).contiguous(), int(keys.numel() - a.numel())
+
+    def NodeRoles(self, threshold=0.05, edges=None, nodes=None, top=4, among="all", min_count=0):
+        """-> _roles.Roles: how every node (or the range nodes=(first, count)) sits in the cover pi[a, k] >= threshold
+        against an adjacency: the training adjacency of the data set (edges=None), or the symmetric one of `edges` (host
+        array or device tensor of (a << 32) | b; duplicates and a == b as written, a key with an end >= N counted in
+        .skipped).  With c[a, k] the neighbours of a in k: .degree, .own, .embedded, .reached, .votes, .squares per node,
+        .home / .hcount / .hflags the `top` (1..16) communities with the largest c (among="all": every k with c >= max(1,
+        min_count); among="own": a's own communities with c >= min_count), .ksum / .ksq / .kmembers per community, all exact
+        integers; .embeddedness, .participation and .z in float64 on the host; .hubs(), .connectors(), .misplaced().  A row
+        of more than 2^25 targets is refused."""
+        from . import _roles
+        threshold, top = _roles.check_threshold(threshold), _roles.check_top(top)
+        _roles.check_among(among)
+        min_count = _roles.check_min_count(min_count)
+        first, count = _roles.check_nodes(nodes, self.cfg.N)
+        op = self._roles()
+        self.drain()
+        if edges is None:
+            (offsets, targets), lost = self._training_adjacency(), 0
+        else:
+            offsets, targets, lost = self._symmetric_csr(edges)
+        st = op.run(self.pi, threshold, offsets, targets, first=first, count=count, among=among, top=top, min_count=min_count)
+        part = lambda name, dt: st[name][first:first + count].cpu().numpy().view(dt)   # noqa: E731
+        whole = lambda name: st[name].cpu().numpy().view(np.uint64)                    # noqa: E731
+        valid, skipped = (int(v) for v in st["counts"].cpu().numpy())
+        return _roles.Roles(threshold, among, top, min_count, part("degree", np.uint32), part("own", np.uint32),
+                            part("embedded", np.uint32), part("reached", np.uint32), part("votes", np.uint64),
+                            part("squares", np.uint64), part("home", np.int32), part("hcount", np.uint32),
+                            part("hflags", np.uint32), whole("ksum"), whole("ksq"), whole("kmembers"), valid, skipped + lost,
+                            N=self.cfg.N, first=first)
