@@ -405,6 +405,95 @@ def depth_group():
     print("depth ok", flush=True)
 
 
+def sparse_overlap(M):
+    """-> [K, K] int64: M.T @ M counted row by row from the members of a row"""
+    K = M.shape[1]
+    sets = [np.flatnonzero(row).astype(np.int64) for row in M]
+    cells, counts = np.unique(np.concatenate([np.add.outer(s * K, s).reshape(-1) for s in sets]), return_counts=True)
+    out = np.zeros(K * K, np.int64)
+    out[cells] = counts
+    return out.reshape(K, K)
+
+
+def big_reference(compact, thr, keys):
+    """the statement over the planted rows and the zero rows of postfit_support's big fixture, the keys remapped to them
+    -> dict(M, words, cells, counts, valid, skipped, links, overlap, top)"""
+    M = members(ps.big_extended(compact), thr)
+    K = M.shape[1]
+    cells, counts, valid, skipped = statement(M, ps.big_remap(keys))
+    C = np.zeros(K * K, np.int64)
+    C[cells] = counts
+    links = C.reshape(K, K) + C.reshape(K, K).T
+    ov = sparse_overlap(M)
+    return dict(M=M, words=words_of(M), cells=cells, counts=counts, valid=valid, skipped=skipped, links=links, overlap=ov,
+                top=selection(ranking(links, ov, "density"), 4, 1))
+
+
+def big_group():
+    """pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, zero but 640 planted rows
+    in four windows): the mask of all rows in the 16-byte form and, from a base 4 bytes past a 16-byte boundary, in the
+    generic form; then edges, finish and top over keys between every two windows, with loops, repeats, ends >= N and ends
+    in zero rows.  The statement is evaluated over the planted rows with the keys remapped; the mask of every other row
+    must be 0.  Only connect_edges_direct exists at this K: connect_edges_runs (K <= 4096) reads no pi, it indexes a mask
+    whose largest word offset at this N is below 2^27, and is left out."""
+    b = Bench()
+    T = b.torch
+    relate = b.ops.CommunityRelations(b.ctx)
+    n, K = ps.BIG_ROWS, ps.BIG_K
+    pi, compact, ids = b.big_pi(62)
+    thr = ps.big_threshold(compact)
+    keys = ps.big_keys(71)
+    ref = big_reference(compact, thr, keys)
+    # a kernel that keeps row * K in 32 bits would give the wrapped figures: each of them that reads pi differs from the
+    # true ones (valid and skipped are counted from the keys alone)
+    wrap = big_reference(ps.big_wrapped(compact), thr, keys)
+    assert (ref["valid"], ref["skipped"]) == (wrap["valid"], wrap["skipped"]) and ref["skipped"] > 20
+    assert not np.array_equal(ref["words"], wrap["words"])
+    assert not (np.array_equal(ref["cells"], wrap["cells"]) and np.array_equal(ref["counts"], wrap["counts"]))
+    assert not np.array_equal(ref["links"], wrap["links"]) and not np.array_equal(ref["overlap"], wrap["overlap"])
+    assert all(not np.array_equal(x, y) for x, y in zip(ref["top"], wrap["top"]))
+    del wrap
+    print("big: the wrapped-offset reference differs in the mask words, directed, links, overlap, partners, their links "
+          "and shared", flush=True)
+    rows = np.concatenate([ids, np.asarray(ps.BIG_ZERO_ROWS, dtype=np.int64)])
+    d_rows = b.ctx.from_numpy(rows)
+
+    def mask_of(pi, form):
+        mask = b.api.mask(pi, thr)
+        assert b.api.kernel_name() == form, b.api.kernel_name()
+        assert tuple(mask.shape) == (n, K // 64)
+        assert np.array_equal(mask[d_rows].cpu().numpy().view(np.uint64), ref["words"]), form + ": the mask words differ"
+        rest = mask.clone()
+        rest[d_rows] = 0
+        assert int(T.count_nonzero(rest)) == 0, form + ": a word of an unplanted row is set"
+        return mask
+
+    mask = mask_of(pi, "connect_mask_fast")
+    force(None)
+    d, cnt = b.api.edges(mask, n, K, keys)
+    assert b.api.kernel_name() == "connect_edges_direct", b.api.kernel_name()
+    want = b.want_dev(K, ref["cells"], ref["counts"])
+    assert T.equal(d.view(-1), want), "directed differs from M[a].T @ M[b]"
+    assert cnt.tolist() == [ref["valid"], ref["skipped"]], (cnt.tolist(), ref["valid"], ref["skipped"])
+    links = b.api.finish(d)
+    assert b.api.kernel_name() == "connect_finish"
+    assert T.equal(links, want.view(K, K) + want.view(K, K).t()), "links differs from C + C.T"
+    d_ov = b.ctx.zeros((K, K), T.int32)
+    relate.pairs(relate.bits(pi, thr), K, n, d_ov)
+    assert T.equal(d_ov, b.ctx.from_numpy(ref["overlap"].astype(np.int32))), "relate's overlap differs from M.T @ M"
+    got = b.api.top(links, d_ov, "density", 4, 1)
+    assert b.api.kernel_name() == "connect_top"
+    for name, x, y, view in zip(("partners", "their links", "shared"), got, ref["top"], (np.int32, np.uint64, np.uint32)):
+        assert np.array_equal(x.cpu().numpy().view(view), y), name + " differ"
+    del pi, d, links, d_ov, want
+    b.release()
+    mis, again, _ = b.big_pi(62, misaligned=True)
+    assert np.array_equal(again, compact)
+    assert T.equal(mask, mask_of(mis, "connect_mask_generic")), "the two forms write other words"
+    print("big ok: %d x %d, thr %.3g, %d keys (%d valid), %d cells linked" % (n, K, thr, keys.size, ref["valid"],
+                                                                             ref["cells"].size), flush=True)
+
+
 def planted_group():
     from mcmc_ammsb_gpu_amd import _connect
     b = Bench()
@@ -576,6 +665,7 @@ GROUPS = {
     "depth": lambda a: depth_group(),
     "forms": lambda a: forms_group(),
     "planted": lambda a: planted_group(),
+    "big": lambda a: big_group(),
     "learner": lambda a: learner_group(a[0] == "1"),
     "cpp": lambda a: cpp_group(),
 }

@@ -337,18 +337,19 @@ def forms_group():
 
 
 def big_group():
-    """K = 8192 and a little over 2^32 elements in one block (17 GB), filled on the device where the members touch it:
-    members among the last rows, against numpy over those rows only"""
+    """K = 8192 and a little over 2^32 elements in one block (17 GB), zeroed and then filled on the device where the
+    members touch it: members among the last rows, against numpy over those rows only; then the same rows in a block whose
+    base is 4 bytes past a 16-byte boundary, which takes the generic form: the same outputs"""
     b = Bench()
     torch = b.torch
     K, tail = 8192, 256
     n = (1 << 32) // K + tail // 2      # the last tail / 2 rows start past element 2^32
-    pi = b.ops.RowPartitionedMatrix(b.ctx, n, K)
-    blk = pi.blocks[0]
+    pi, blk = b.zeroed(n, K)
     gen = torch.Generator(device=blk.device)
     gen.manual_seed(9)
     r = torch.rand((tail, K), generator=gen, device=blk.device).pow_(64).clamp_(min=1e-24)
-    blk[n - tail:].copy_(r / r.sum(1, keepdim=True))
+    r = r / r.sum(1, keepdim=True)
+    blk[n - tail:].copy_(r)
     host_tail = blk[n - tail:].cpu().numpy()
     thr = float(np.sort(host_tail.reshape(-1))[-40 * tail])     # about 40 memberships per node
     rng = np.random.default_rng(53)
@@ -361,6 +362,14 @@ def big_group():
     got = b.match(pi, thr, off, mem, dsize=dsize)
     assert b.cv.last_kernel_name() == "cover_fast"
     check(got, ref, "beyond 2^32 elements")
+    del pi, blk
+    b.release()
+    mis, blk = b.zeroed(n, K, misaligned=True)
+    blk[n - tail:].copy_(r)
+    got2 = b.match(mis, thr, off, mem, dsize=dsize)
+    assert b.cv.last_kernel_name() == "cover_generic"
+    check(got2, ref, "beyond 2^32 elements, misaligned base")
+    assert all(np.array_equal(got[name], got2[name]) for name in got)
     print("big ok: %d x %d" % (n, K), flush=True)
 
 

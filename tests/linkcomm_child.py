@@ -314,18 +314,20 @@ def forms_group():
 
 
 def big_group():
-    """K = 8192 and a little over 2^32 elements in one block (17 GB), filled on the device where the edges touch it:
-    512 edges among the last rows, against numpy over the gathered rows only"""
+    """K = 8192 and a little over 2^32 elements in one block (17 GB), zeroed and then filled on the device where the
+    edges touch it: 512 edges among the last rows, against numpy over the gathered rows only; then the same rows in a
+    block whose base is 4 bytes past a 16-byte boundary, which takes the generic form: the same ids, terms and sizes, prob
+    under its bound"""
     b = Bench()
     torch = b.torch
     K, tail = 8192, 256
     n = (1 << 32) // K + tail // 2      # the last tail / 2 rows start past element 2^32
-    pi = b.ops.RowPartitionedMatrix(b.ctx, n, K)
-    blk = pi.blocks[0]
+    pi, blk = b.zeroed(n, K)
     gen = torch.Generator(device=blk.device)
     gen.manual_seed(8)
     r = torch.rand((tail, K), generator=gen, device=blk.device).pow_(64).clamp_(min=1e-24)
-    blk[n - tail:].copy_(r / r.sum(1, keepdim=True))
+    r = r / r.sum(1, keepdim=True)
+    blk[n - tail:].copy_(r)
     rng = np.random.default_rng(33)
     beta_h = draw_beta(rng, K)
     host_tail = blk[n - tail:].cpu().numpy()
@@ -334,10 +336,23 @@ def big_group():
     edges = ((u + np.uint64(n - tail)) << np.uint64(32)) | (v + np.uint64(n - tail))
     edges = np.concatenate([edges, [(np.uint64(n) << np.uint64(32)) | np.uint64(n - 1), np.uint64(n - 1) << np.uint64(32) | np.uint64(n - 1)]])
     local = np.concatenate([local, [(np.uint64(tail) << np.uint64(32)) | np.uint64(tail - 1), np.uint64(tail - 1) << np.uint64(32) | np.uint64(tail - 1)]])
+    refs, fast = {}, {}
     for T in (1, 16):
-        got = b.call(pi, b.dev(beta_h), edges, T)
+        refs[T] = reference(host_tail, beta_h, EPS, local, T, 0.0)
+        fast[T] = b.call(pi, b.dev(beta_h), edges, T)
         assert b.lc.last_kernel_name() == "linkcomm_fast_v4_chunked"
-        check(got, reference(host_tail, beta_h, EPS, local, T, 0.0), K, "beyond 2^32 elements, T=%d" % T)
+        check(fast[T], refs[T], K, "beyond 2^32 elements, T=%d" % T)
+    del pi, blk
+    b.release()
+    mis, blk = b.zeroed(n, K, misaligned=True)
+    blk[n - tail:].copy_(r)
+    for T in (1, 16):
+        got = b.call(mis, b.dev(beta_h), edges, T)
+        assert b.lc.last_kernel_name() == "linkcomm_generic"
+        check(got, refs[T], K, "beyond 2^32 elements, misaligned base, T=%d" % T)
+        # ids, terms and sizes are exact in both forms; prob is a sum whose order the form decides (layout_group)
+        assert np.array_equal(got[0], fast[T][0]) and np.array_equal(got[1].view(np.uint32), fast[T][1].view(np.uint32))
+        assert np.array_equal(got[3], fast[T][3])
     print("big ok: %d x %d" % (n, K), flush=True)
 
 

@@ -342,10 +342,9 @@ def big_group():
     print("big ok: %d x %d" % (N, K), flush=True)
     del pi, blk
     torch.cuda.empty_cache()
-    # K = 8192 and a little over 2^32 elements in one block: queries and candidates in the last 4096 rows
+    # K = 8192 and a little over 2^32 elements in one block, zeroed: queries and candidates in the last 4096 rows
     K, n = 8192, 524288 + 4096
-    pi = b.ops.RowPartitionedMatrix(b.ctx, n, K)
-    blk = pi.blocks[0]
+    pi, blk = b.zeroed(n, K)
     tail = 4096
     r = torch.rand((tail, K), generator=gen, device=blk.device).pow_(64).clamp_(min=1e-24)
     blk[n - tail:].copy_(r / r.sum(1, keepdim=True))

@@ -230,6 +230,61 @@ def cut_group():
     print("cut ok", flush=True)
 
 
+def big_group():
+    """pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, zero but 640 planted rows
+    in four windows): run() over connect's keys of that fixture, with the mask in the 16-byte form and, from a base 4 bytes
+    past a 16-byte boundary, in the generic form.  The statement is evaluated over the planted rows and the zero rows with
+    the keys remapped; the degree of every other row must be 0.  The forms are modularity_edges_w2 / modularity_nodes_w2
+    at this K; the _w1 forms (K <= 4096) read no pi, they index a mask whose largest word offset at this N is below 2^27,
+    and are left out."""
+    b = Bench()
+    T = b.torch
+    n, K = ps.BIG_ROWS, ps.BIG_K
+    pi, compact, ids = b.big_pi(64)
+    thr = ps.big_threshold(compact)
+    keys = ps.big_keys(71)
+    local = ps.big_remap(keys)
+    IN, SV, deg, valid, skipped = statement(members(ps.big_extended(compact), thr), local)
+    # a kernel that keeps row * K in 32 bits would give the wrapped figures: those that read pi differ from the true
+    # ones (the degrees, valid and skipped are counted from the keys alone)
+    wIN, wSV, wdeg, wvalid, wskipped = statement(members(ps.big_extended(ps.big_wrapped(compact)), thr), local)
+    assert IN != wIN and SV != wSV and np.array_equal(deg, wdeg) and (valid, skipped) == (wvalid, wskipped)
+    assert sum(v > 0 for v in IN) > 100 and skipped > 20 and deg[640:].all()
+    print("big: the wrapped-offset reference differs in internal and volume", flush=True)
+    rows = np.concatenate([ids, np.asarray(ps.BIG_ZERO_ROWS, dtype=np.int64)])
+    d_rows = b.ctx.from_numpy(rows)
+
+    def run(pi, mform):
+        internal, volume, counts, degree = b.api.run(pi, thr, keys)
+        assert b.api.kernel_name() == "modularity_nodes_w2", b.api.kernel_name()
+        wide = lambda t: b.md.wide(t.cpu().numpy().view(np.uint64)).tolist()   # noqa: E731
+        assert counts.cpu().numpy().tolist() == [valid, skipped], mform
+        assert wide(internal) == IN, mform + ": internal differs from the statement"
+        assert wide(volume) == SV, mform + ": volume differs from the statement"
+        assert tuple(degree.shape) == (n,)
+        assert np.array_equal(degree[d_rows].cpu().numpy().view(np.uint32), deg), mform + ": degrees differ"
+        rest = degree.clone()
+        rest[d_rows] = 0
+        assert int(T.count_nonzero(rest)) == 0, mform + ": a node without a key has a degree"
+        # the calls of run() one by one: the names of the forms that ran
+        mask = b.links.mask(pi, float(F32(thr)))
+        assert b.links.kernel_name() == mform, b.links.kernel_name()
+        state = b.api.edges(mask, n, K, keys)
+        assert b.api.kernel_name() == "modularity_edges_w2", b.api.kernel_name()
+        assert T.equal(state[1], internal) and T.equal(state[0], degree) and T.equal(state[2], counts)
+        return internal, volume, counts, degree
+
+    first = run(pi, "connect_mask_fast")
+    del pi
+    b.release()
+    mis, again, _ = b.big_pi(64, misaligned=True)
+    assert np.array_equal(again, compact)
+    second = run(mis, "connect_mask_generic")
+    assert all(T.equal(x, y) for x, y in zip(first, second)), "the two forms of the mask give other sums"
+    print("big ok: %d x %d, thr %.3g, %d valid keys, %d communities with a link inside" % (
+        n, K, thr, valid, sum(v > 0 for v in IN)), flush=True)
+
+
 def cross_group():
     """on a partition internal[k] == CommunityQuality's internal[k] << 62 and volume[k] == (2 internal + boundary)[k] << 62"""
     b = Bench()
@@ -366,6 +421,7 @@ GROUPS = {
     "cut": lambda a: cut_group(),
     "cross": lambda a: cross_group(),
     "planted": lambda a: planted_group(),
+    "big": lambda a: big_group(),
     "learner": lambda a: learner_group(a[0] == "1"),
     "cpp": lambda a: cpp_group(),
 }

@@ -280,6 +280,89 @@ def forms_group():
     print("forms ok", flush=True)
 
 
+def big_cover(rng, G=36):
+    """G communities over the rows of postfit_support's big fixture, in global numbering: 5 to 60 planted rows each, a
+    third of them with rows >= 2^19 only or with rows of the first window only; into the first ones go members >= N (N
+    itself, a little past it, 2^32 - 1), which are skipped, and zero rows, which are valid and outside the universe"""
+    ids = ps.big_ids()
+    pools = (ids, ids[ids >= (1 << 19)], ids[:128])
+    lists = [rng.choice(pools[g % 3], int(rng.integers(5, 61)), replace=False).astype(np.uint32) for g in range(G)]
+    past = (ps.BIG_ROWS, ps.BIG_ROWS + 5, NONE)
+    for j, z in enumerate(ps.BIG_ZERO_ROWS):
+        lists[j] = np.concatenate([lists[j], np.array([z, past[j % 3]], dtype=np.uint32)])
+        lists[j + 7] = np.concatenate([np.array([past[(j + 1) % 3], z], dtype=np.uint32), lists[j + 7]])
+    offsets = np.zeros(G + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([c.size for c in lists])
+    return offsets, np.concatenate(lists).astype(np.uint32)
+
+
+def big_group():
+    """pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, zero but 640 planted rows
+    in four windows): the detected bits of the 640 planted rows as the universe, and of the last window alone, in the
+    16-byte form and, from a base 4 bytes past a 16-byte boundary, in the generic form; then the truth bits and the pair
+    pass against a ground truth over the planted rows with members >= N and members in zero rows.  The statement is
+    evaluated over the planted rows and the zero rows, the members remapped.  omega_truth_* and omega_pairs read no pi:
+    they are checked here on what the detected bits gave them."""
+    b = Bench()
+    n, K = ps.BIG_ROWS, ps.BIG_K
+    pi, compact, ids = b.big_pi(63)
+    thr = ps.big_threshold(compact)
+    off, mem = big_cover(np.random.default_rng(73))
+    local = ps.big_positions(mem).astype(np.uint32)
+    universes = {"planted": ids.astype(np.uint32), "last window": ids[ids >= (1 << 19) - 128].astype(np.uint32)}
+    ext = ps.big_extended(compact)
+    refs, words = {}, {}                        # (words: what the bit words of two rows must share)
+    wext = ps.big_extended(ps.big_wrapped(compact))
+    for name, U in universes.items():
+        pos = ps.big_positions(U).astype(np.uint32)
+        refs[name] = statement(ext, thr, off, local, pos)
+        MD = (ext[pos] >= F32(thr)).astype(F32)
+        words[name] = MD @ MD.T                    # shared communities of every two positions (exact: below 2^24)
+        # a kernel that keeps row * K in 32 bits would give the wrapped figures: each of them that reads pi differs
+        # from the true ones (the truth histogram, skipped and outside are counted from the ground truth alone)
+        wrap = statement(wext, thr, off, local, pos)
+        WD = (wext[pos] >= F32(thr)).astype(F32)
+        assert not np.array_equal(words[name], WD @ WD.T)
+        assert not np.array_equal(refs[name]["dcount"], wrap["dcount"])
+        assert not np.array_equal(refs[name]["detected"], wrap["detected"]) and not np.array_equal(refs[name]["agree"], wrap["agree"])
+        assert refs[name]["skipped"] == 8 and refs[name]["outside"] >= 8 and refs[name]["truth"][1:].sum() > 0
+    print("big: the wrapped-offset reference differs in the communities two rows share, the counts per node and the "
+          "detected and agree histograms, for both universes", flush=True)
+
+    def run(pi, form):
+        out = {}
+        for name, U in universes.items():
+            got = b.run(pi, thr, off, mem, U, [(0, tiles_of(U.size))])
+            assert form in SEEN and "omega_pairs" in SEEN, SEEN
+            ref = refs[name]
+            assert got["L"] == ref["L"], (name, got["L"], ref["L"])
+            assert np.array_equal(got["dcount"], ref["dcount"]) and np.array_equal(got["tcount"], ref["tcount"]), name
+            check(got, ref, "%s universe=%s" % (form, name))
+            bits, counts = b.api.detected_bits(pi, thr, nodes=b.ctx.from_numpy(U))
+            assert b.api.kernel_name() == form, b.api.kernel_name()
+            # which bit stands for which community is private to the library: the bits are held to what any placement
+            # must give, the members per row and the communities shared by every two rows
+            B = np.unpackbits(bits.cpu().numpy().view(np.uint8), axis=1).astype(F32)
+            assert B.shape == (U.size, K) and np.array_equal(B.sum(1), ref["dcount"]), "%s universe=%s: set bits per row" % (form, name)
+            assert np.array_equal(B @ B.T, words[name]), "%s universe=%s: the bits two rows share differ" % (form, name)
+            assert np.array_equal(counts.cpu().numpy(), ref["dcount"])
+            out[name] = (got, bits)
+        return out
+
+    first = run(pi, "omega_bits_fast")
+    del pi
+    b.release()
+    SEEN.clear()
+    mis, again, _ = b.big_pi(63, misaligned=True)
+    assert np.array_equal(again, compact)
+    second = run(mis, "omega_bits_generic")
+    for name in universes:
+        assert same(first[name][0], second[name][0]) and b.torch.equal(first[name][1], second[name][1]), \
+            "universe=%s: the two forms differ" % name
+    r = refs["planted"]
+    print("big ok: %d x %d, thr %.3g, L %d, skipped %d, outside %d" % (n, K, thr, r["L"], r["skipped"], r["outside"]), flush=True)
+
+
 def persistent_group():
     """n = 3000 is 300 tiles, run also as one launch per 7 tiles; n = 4200 is 561 tiles, more than the 512 blocks of the
     grid, so that blocks go round the persistent loop"""
@@ -416,6 +499,7 @@ GROUPS = {
     "planted": lambda a: planted_group(),
     "forms": lambda a: forms_group(),
     "persistent": lambda a: persistent_group(),
+    "big": lambda a: big_group(),
     "learner": lambda a: learner_group(a[0] == "1"),
     "cpp": lambda a: cpp_group(),
 }

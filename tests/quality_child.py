@@ -301,18 +301,20 @@ def forms_group():
 
 
 def big_group():
-    """K = 8192 and a little over 2^32 elements in one block (17 GB), filled on the device where the edges touch it:
-    members and edges among the last rows, against numpy over those rows only"""
+    """K = 8192 and a little over 2^32 elements in one block (17 GB), zeroed and then filled on the device where the
+    edges touch it: members and edges among the last rows, against numpy over those rows only; then the same rows in a
+    block whose base is 4 bytes past a 16-byte boundary, which takes the generic mask form: the same mask, the same
+    counts"""
     b = Bench()
     torch = b.torch
     K, tail = 8192, 256
     n = (1 << 32) // K + tail // 2      # the last tail / 2 rows start past element 2^32
-    pi = b.ops.RowPartitionedMatrix(b.ctx, n, K)
-    blk = pi.blocks[0]
+    pi, blk = b.zeroed(n, K)
     gen = torch.Generator(device=blk.device)
     gen.manual_seed(9)
     r = torch.rand((tail, K), generator=gen, device=blk.device).pow_(64).clamp_(min=1e-24)
-    blk[n - tail:].copy_(r / r.sum(1, keepdim=True))
+    r = r / r.sum(1, keepdim=True)
+    blk[n - tail:].copy_(r)
     host_tail = blk[n - tail:].cpu().numpy()
     thr = float(np.sort(host_tail.reshape(-1))[-40 * tail])     # about 40 memberships per node
     rng = np.random.default_rng(43)
@@ -333,6 +335,16 @@ def big_group():
     ref = reference(host_tail, thr, local)
     assert ref[0][:K].sum() > 0 and ref[0][2 * K + 1] == 1
     check(got, ref, "beyond 2^32 elements")
+    del pi, blk
+    b.release()
+    mis, blk = b.zeroed(n, K, misaligned=True)
+    blk[n - tail:].copy_(r)
+    again = b.mask(mis, thr)
+    assert b.q.last_kernel_name() == "quality_mask_generic"
+    assert torch.equal(mask, again), "the generic form's bytes differ from the fast form's"
+    got2 = b.edges(again, n, K, edges)
+    check(got2, ref, "beyond 2^32 elements, misaligned base")
+    assert all(np.array_equal(x, y) for x, y in zip(got, got2))
     print("big ok: %d x %d" % (n, K), flush=True)
 
 

@@ -185,18 +185,23 @@ def ties_group():
 
 
 def big_group():
-    """K = 8192 and a little over 2^32 elements in ONE block: the last rows are only reachable with 64-bit offsets"""
+    """K = 8192 and a little over 2^32 elements in ONE block: the last rows are only reachable with 64-bit offsets.  Then
+    the same values in a block whose base is 4 bytes past a 16-byte boundary, which takes the generic form: the same
+    outputs"""
     b = Bench()
     torch = b.torch
     K, n = 8192, 524288 + 4096
     assert n * K > 1 << 32
-    pi = b.ops.RowPartitionedMatrix(b.ctx, n, K)
-    blk = pi.blocks[0]
-    gen = torch.Generator(device=blk.device)
-    gen.manual_seed(5)
     step = 32768
-    for lo in range(0, n, step):   # values >= 0, a few large ones per row (u^64), rows not normalised: any finite >= 0
-        blk[lo:lo + step].copy_(torch.rand((min(step, n - lo), K), generator=gen, device=blk.device).pow_(64))
+
+    def fill(blk):
+        gen = torch.Generator(device=blk.device)
+        gen.manual_seed(5)
+        for lo in range(0, n, step):   # values >= 0, a few large ones per row (u^64), rows not normalised: any finite >= 0
+            blk[lo:lo + step].copy_(torch.rand((min(step, n - lo), K), generator=gen, device=blk.device).pow_(64))
+
+    pi, blk = b.zeroed(n, K)
+    fill(blk)
     thr, T = 0.25, 4
     sizes = b.ctx.zeros((K,), torch.int64)
     tail = 4096
@@ -206,13 +211,27 @@ def big_group():
     host_tail = blk[n - tail:].cpu().numpy()
     same(got, expected(host_tail, T, thr), "beyond 2^32 elements: last %d rows" % tail)
     nodes = np.array([n - 1, n - 2, 0, n - 4096], dtype=np.uint32)
-    same(b.ro.top(pi, 16, 0.0, nodes=nodes), expected(blk[torch.from_numpy(nodes.astype(np.int64)).to(blk.device)].cpu().numpy(), 16, 0.0),
+    listed = b.ro.top(pi, 16, 0.0, nodes=nodes)
+    same(listed, expected(blk[torch.from_numpy(nodes.astype(np.int64)).to(blk.device)].cpu().numpy(), 16, 0.0),
          "beyond 2^32 elements: node list")
     b.ro.sizes(pi, thr, out=sizes)
     want = np.zeros(K, dtype=np.int64)
     for lo in range(0, n, step):
         want += (blk[lo:lo + step].cpu().numpy() >= np.float32(thr)).sum(0)
     assert np.array_equal(sizes.cpu().numpy(), want), "sizes over %d rows" % n
+    del pi, blk
+    b.release()
+    mis, blk = b.zeroed(n, K, misaligned=True)
+    fill(blk)
+    assert np.array_equal(blk[n - tail:].cpu().numpy(), host_tail)
+    got2 = b.ro.top(mis, T, thr, rows=(n - tail, n))
+    assert b.ro.kernel_name() == "readout_generic"
+    listed2 = b.ro.top(mis, 16, 0.0, nodes=nodes)
+    assert b.ro.kernel_name() == "readout_generic"
+    sizes2 = b.ro.sizes(mis, thr)
+    assert b.ro.kernel_name() == "readout_generic"
+    for x, y in zip(got + listed + (sizes,), got2 + listed2 + (sizes2,)):
+        assert torch.equal(x, y), "the generic form's outputs differ from the fast form's"
     print("big ok: %d x %d (%.1f GB), sizes sum %d" % (n, K, n * K * 4 / 1e9, int(want.sum())), flush=True)
 
 

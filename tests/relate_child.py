@@ -277,6 +277,92 @@ def forms_group():
     print("forms ok", flush=True)
 
 
+def sparse_overlap(M):
+    """-> (cells k K + l ascending, counts): the non-zero entries of M.T @ M, counted row by row from the members of a row"""
+    K = M.shape[1]
+    sets = [np.flatnonzero(row).astype(np.int64) for row in M]
+    flat = np.concatenate([np.add.outer(s * K, s).reshape(-1) for s in sets])
+    cells, counts = np.unique(flat, return_counts=True)
+    return cells, counts.astype(np.int64)
+
+
+def dense_of(K, cells, counts):
+    out = np.zeros(K * K, np.int64)
+    out[cells] = counts
+    return out.reshape(K, K)
+
+
+def big_group():
+    """pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, zero but 640 planted rows
+    in four windows): the bits of all rows and of the slab that starts 128 rows before element 2^32, in the 16-byte form
+    and, from a base 4 bytes past a 16-byte boundary, in the generic form; overlap and partners of the full bits.  The
+    statement is evaluated over the 640 rows; every word of the other rows must be 0.  relate_pairs and relate_top read
+    no pi: they are checked here on what the bits gave them, not reached past 2^32 themselves."""
+    b = Bench()
+    T = b.torch
+    n, K = ps.BIG_ROWS, ps.BIG_K
+    slab = ((1 << 19) - 128, n)
+    pi, compact, ids = b.big_pi(61)
+    thr = ps.big_threshold(compact)
+    M, Mw = members(compact, thr), members(ps.big_wrapped(compact), thr)
+    assert np.array_equal(ids & 63, np.arange(640) & 63)     # a window begins and ends on a word of 64 rows
+    cols = np.unique(ids >> 6)
+    want, wrapped = words_of(M, 0, 640), words_of(Mw, 0, 640)
+    tail = want[:, -4:].copy()                               # the slab's words
+    cells, counts = sparse_overlap(M)
+    wcells, wcounts = sparse_overlap(Mw)
+    ov = dense_of(K, cells, counts)
+    wp, ws = selection(ranking(ov, "jaccard"), 4, 1)
+    # a kernel that keeps row * K in 32 bits would give the wrapped figures: each of them differs from the true ones
+    assert M.sum() >= 40 * 640 and cols.size == 10 == want.shape[1]
+    assert not np.array_equal(want, wrapped) and not np.array_equal(tail, wrapped[:, -4:])
+    assert not (np.array_equal(cells, wcells) and np.array_equal(counts, wcounts))
+    wov = dense_of(K, wcells, wcounts)
+    assert not np.array_equal(np.diagonal(ov), np.diagonal(wov))
+    wwp, wws = selection(ranking(wov, "jaccard"), 4, 1)
+    assert not np.array_equal(wp, wwp) and not np.array_equal(ws, wws)
+    del wov
+    print("big: the wrapped-offset reference differs in the words, the slab's words, overlap, its diagonal, partners "
+          "and shared", flush=True)
+    d_cols = b.ctx.from_numpy(cols)
+
+    def bits_of(pi, form):
+        full = b.api.bits(pi, thr)
+        assert b.api.kernel_name() == form, b.api.kernel_name()
+        assert tuple(full.shape) == (K, n // 64)
+        got = full[:, d_cols].cpu().numpy().view(np.uint64)
+        assert np.array_equal(got, want), "%s: the words of the planted rows differ" % form
+        rest = full.clone()
+        rest[:, d_cols] = 0
+        assert int(T.count_nonzero(rest)) == 0, "%s: a word of an unplanted row is set" % form
+        del rest
+        part = b.api.bits(pi, thr, rows=slab)
+        assert b.api.kernel_name() == form, b.api.kernel_name()
+        assert tuple(part.shape) == (K, 4)
+        assert np.array_equal(part.cpu().numpy().view(np.uint64), tail), "%s: the words of the slab differ" % form
+        return full, part
+
+    full, part = bits_of(pi, "relate_bits_fast")
+    d_ov = b.ctx.zeros((K, K), T.int32)
+    b.api.pairs(full, K, n, d_ov)
+    assert b.api.kernel_name() == "relate_pairs"
+    d_want = b.ctx.zeros((K * K,), T.int32)
+    d_want[b.ctx.from_numpy(cells)] = b.ctx.from_numpy(counts.astype(np.int32))
+    assert T.equal(d_ov.view(-1), d_want), "overlap differs from M.T @ M over the planted rows"
+    assert np.array_equal(d_ov.diagonal().cpu().numpy().astype(np.int64), M.sum(0)), "the diagonal is not the column sums"
+    partner, shared = b.api.top(d_ov, "jaccard", 4, 1)
+    assert b.api.kernel_name() == "relate_top"
+    assert np.array_equal(partner.cpu().numpy(), wp), "partners differ"
+    assert np.array_equal(shared.cpu().numpy().view(np.uint32), ws), "shared differs"
+    del pi, d_ov, d_want
+    b.release()
+    mis, again, _ = b.big_pi(61, misaligned=True)
+    assert np.array_equal(again, compact)
+    mfull, mpart = bits_of(mis, "relate_bits_generic")
+    assert T.equal(full, mfull) and T.equal(part, mpart), "the two forms write other words"
+    print("big ok: %d x %d, thr %.3g, %d memberships, %d overlapping pairs" % (n, K, thr, int(M.sum()), cells.size), flush=True)
+
+
 def planted_group():
     from mcmc_ammsb_gpu_amd import _relate
     b = Bench()
@@ -424,6 +510,7 @@ GROUPS = {
     "depth": lambda a: depth_group(),
     "forms": lambda a: forms_group(),
     "planted": lambda a: planted_group(),
+    "big": lambda a: big_group(),
     "learner": lambda a: learner_group(a[0] == "1"),
     "cpp": lambda a: cpp_group(),
 }

@@ -273,6 +273,77 @@ def cut_group():
     print("cut ok", flush=True)
 
 
+def big_group():
+    """pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, zero but 640 planted rows
+    in four windows): run() over the adjacency of connect's keys of that fixture (offsets [N + 1], a target only in the
+    rows of the planted nodes and of four zero rows; targets >= N among them), with the mask in the 16-byte form and, from
+    a base 4 bytes past a 16-byte boundary, in the generic form; a second state filled by two calls that cut the nodes
+    128 rows before element 2^32.  The statement is evaluated over the planted rows and the zero rows in compact
+    numbering; every other node's entries must be 0 (home: the empty slot).  The form is roles_nodes_w2 at this K;
+    roles_nodes_w1 (K <= 4096) reads no pi, it indexes a mask whose largest word offset at this N is below 2^27, and is
+    left out."""
+    b = Bench()
+    T = b.torch
+    n, K = ps.BIG_ROWS, ps.BIG_K
+    how = ("all", 4, 0)
+    cut = (1 << 19) - 128
+    pi, compact, ids = b.big_pi(65)
+    thr = ps.big_threshold(compact)
+    keys = ps.big_keys(71)
+    off, tgt = ps.big_csr(keys, n)
+    rows = np.concatenate([ids, np.asarray(ps.BIG_ZERO_ROWS, dtype=np.int64)])
+    loff, ltgt = ps.big_csr(ps.big_remap(keys), rows.size)
+    base, slots = statement(members(ps.big_extended(compact), thr), loff, ltgt, [how])
+    # a kernel that keeps row * K in 32 bits would give the wrapped figures: those that read pi differ from the true
+    # ones (the degrees, valid and skipped are counted from the adjacency alone)
+    wbase, wslots = statement(members(ps.big_extended(ps.big_wrapped(compact)), thr), loff, ltgt, [how])
+    differs = [name for name in NODE32 + NODE64 + SUMS if not np.array_equal(base[name], wbase[name])]
+    assert differs == [name for name in NODE32 + NODE64 + SUMS if name != "degree"], differs
+    assert all(not np.array_equal(x, y) for x, y in zip(slots[0], wslots[0])) and base["counts"] == wbase["counts"]
+    assert base["counts"][1] > 20 and base["degree"][640:].all() and not base["own"][640:].any()
+    print("big: the wrapped-offset reference differs in %s, home, hcount and hflags" % ", ".join(differs), flush=True)
+    d_rows, d_off, d_tgt = b.ctx.from_numpy(rows), b.dev(off), b.dev(tgt)
+    views = dict(home=np.int32, votes=np.uint64, squares=np.uint64)
+
+    def check_state(st, what):
+        want = dict(base, home=slots[0][0], hcount=slots[0][1], hflags=slots[0][2])
+        for name in NODE32 + NODE64 + ("home", "hcount", "hflags"):
+            t = st[name]
+            assert t.shape[0] == n, name
+            got = t[d_rows].cpu().numpy().view(views.get(name, np.uint32))
+            assert np.array_equal(got, want[name]), "%s: %s differs from the statement" % (what, name)
+            rest = t.clone()
+            rest[d_rows] = -1 if name == "home" else 0
+            empty = int(T.count_nonzero(rest + 1 if name == "home" else rest))
+            assert empty == 0, "%s: %s of a node without a target and without a member is not empty" % (what, name)
+        for name in SUMS:
+            assert st[name].cpu().numpy().view(np.uint64).tolist() == base[name], "%s: %s differs" % (what, name)
+        assert st["counts"].cpu().numpy().tolist() == base["counts"], what + ": counts differ"
+
+    def run(pi, mform):
+        st = b.api.run(pi, thr, d_off, d_tgt, among=how[0], top=how[1], min_count=how[2])
+        assert b.api.kernel_name() == "roles_nodes_w2", b.api.kernel_name()
+        check_state(st, mform)
+        mask = b.links.mask(pi, float(F32(thr)))
+        assert b.links.kernel_name() == mform, b.links.kernel_name()
+        two = b.api.state(n, K, how[1])
+        for first, count in ((0, cut), (cut, n - cut)):
+            b.api.nodes(mask, n, K, d_off, d_tgt, first=first, count=count, among=how[0], top=how[1], min_count=how[2], state=two)
+            assert b.api.kernel_name() == "roles_nodes_w2", b.api.kernel_name()
+        assert sorted(two) == sorted(st) and all(T.equal(two[name], st[name]) for name in st), \
+            mform + ": two calls cut at node %d differ from one" % cut
+        return st
+
+    first = run(pi, "connect_mask_fast")
+    del pi
+    b.release()
+    mis, again, _ = b.big_pi(65, misaligned=True)
+    assert np.array_equal(again, compact)
+    second = run(mis, "connect_mask_generic")
+    assert all(T.equal(first[name], second[name]) for name in first), "the two forms of the mask give other states"
+    print("big ok: %d x %d, thr %.3g, %d valid targets, %d skipped" % (n, K, thr, base["counts"][0], base["counts"][1]), flush=True)
+
+
 def cross_group():
     """from one edge list, both orders of the ends, duplicates and loops included, through the learner's other analyses"""
     from modularity_child import edge_list
@@ -426,6 +497,7 @@ GROUPS = {
     "cut": lambda a: cut_group(),
     "cross": lambda a: cross_group(),
     "planted": lambda a: planted_group(),
+    "big": lambda a: big_group(),
     "learner": lambda a: learner_group(a[0] == "1"),
     "cpp": lambda a: cpp_group(),
 }

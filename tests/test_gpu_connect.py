@@ -20,6 +20,13 @@ One child process per group (connect_child.py):
   planted  two disjoint columns with every link between them (density exactly 1.0, in bridged()); disjoint columns
            without a link between them have no partner; ties to the lower id; a pair of communities without a pair of
            distinct nodes is no partner by density.
+  big      pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, 17 GB, zero but 640
+           planted rows in four windows that straddle byte offset 2^32, element 2^31 and element 2^32): the mask as
+           connect_mask_fast and, from a base 4 bytes past a 16-byte boundary, as connect_mask_generic, equal to the
+           statement's words on the planted rows and 0 elsewhere; edges (connect_edges_direct, the only form at this K),
+           finish and top over keys between every two windows with loops, repeats, ends >= N and ends in zero rows.  The
+           inputs are first shown to tell a wrapped 32-bit offset apart in every figure that reads pi.
+           connect_edges_runs (K <= 4096) reads no pi and is left out.
   learner  bench.py's C1 after 30 steps (eager and graph launch): CommunityLinks and LinkedCommunities against the
            statement over the checkpointed pi and the data set's training links; the diagonal against CommunityQuality;
            Run(20) + the calls + Run(20) leaves the checkpoint buffers Run(40) leaves.  No property of the fitted cover is
@@ -54,6 +61,10 @@ def test_every_kernel_form_is_named_and_reached():
 
 def test_planted_bridges_disjoint_columns_ties_and_empty_pairs():
     _run(["planted"], "planted ok", 120)
+
+
+def test_pi_past_element_2_32_in_both_forms():
+    _run(["big"], "big ok", 300)
 
 
 @pytest.mark.parametrize("graph", [0, 1])

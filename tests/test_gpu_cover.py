@@ -16,7 +16,8 @@ One child process per group (cover_child.py):
   layout   pi as one, two and eleven-plus-a-ragged-one blocks; a misaligned block base takes the generic form at
            K = 256 and gives the same results.
   forms    every counting form is named and reached, at K on both sides of every chunk boundary.
-  big      K = 8192 beyond 2^32 elements (17 GB), members among the last rows.
+  big      K = 8192 beyond 2^32 elements (17 GB, zeroed), members among the last rows; again from a base 4 bytes past a
+           16-byte boundary: cover_generic, the same outputs.
   constructed  pi built from the generator's planted cover under a known column permutation: the match is the
            permutation and every F1 is exactly 1; one community halved has the hand-computed F1.
   learner  Learner.CompareCover on bench.py's C1 after 30 steps (eager and graph launch) with hostlib.generate_cover

@@ -13,7 +13,8 @@ One child process per group (linkcomm_child.py):
            next edge requested before the rounds, the chunked hand-over, several edges per counter), special edges past 8192.
   layout   pi as one, two and eleven-plus-a-ragged-one blocks; a misaligned block base (generic at K = 256).
   forms    every kernel form the dispatcher can select is named and reached.
-  big      K = 8192 beyond 2^32 elements (17 GB), 512 edges among the last rows.
+  big      K = 8192 beyond 2^32 elements (17 GB, zeroed), 512 edges among the last rows; again from a base 4 bytes past
+           a 16-byte boundary: linkcomm_generic, the same ids, terms and sizes.
   learner  Learner.TrainingLinks / LinkCommunities / LinkCommunitySizes on bench.py's C1 after 30 steps (eager and
            graph launch); slabs; Run(20) + the calls + Run(20) leaves the checkpoint buffers Run(40) leaves.
   cpp      tests/cpp/linkcomm_test.cc; its file and ammsb_main --link-communities-out parsed back and compared with

@@ -12,7 +12,8 @@ One child process per group (linkpred_child.py):
              inside a batch of 200; two calls bit-equal; identical candidate rows spread over the whole range.
   layout     pi as one, two and eleven-plus-a-ragged-one blocks; cand_lo and the end inside a block.
   forms      every kernel form the dispatchers can select is named and reached.
-  big        N = 10^6, K = 1024 (4.1 GB), Q = 64, T = 10 with the tie-tolerant check; K = 8192 beyond 2^32 elements.
+  big        N = 10^6, K = 1024 (4.1 GB), Q = 64, T = 10 with the tie-tolerant check; K = 8192 beyond 2^32 elements
+             (a zeroed block).
   planted    a constructed model whose AUC is exactly 1 (and 0 with the labels flipped).
   learner    Learner.LinkProbabilities / PredictLinks / HeldoutAUC on bench.py's C1 after 30 steps (eager and graph
              launch); slabs; Run(20) + the three calls + Run(20) leaves the checkpoint buffers Run(40) leaves.

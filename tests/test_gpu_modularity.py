@@ -19,6 +19,12 @@ One child process per group (modularity_child.py):
            statement; against the unquantised rationals |dq_k| <= 8 2^-53 (2 in_k + s_k^2 / 2m) / 2m + 2^-36 |q_k| (the
            float64 rounding of the four operations, and the fixed-point bound at the library's limits: derived, not
            measured).
+  big      pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, 17 GB, zero but 640
+           planted rows in four windows that straddle byte offset 2^32, element 2^31 and element 2^32): run() over the
+           keys of connect's big group, the mask as connect_mask_fast and, from a base 4 bytes past a 16-byte boundary, as
+           connect_mask_generic; internal, volume and counts equal the statement's 128-bit integers, degree [N] equals it
+           on the planted rows and is 0 elsewhere (modularity_edges_w2 / _nodes_w2).  The inputs are first shown to tell
+           a wrapped 32-bit offset apart in internal and volume.  The _w1 forms (K <= 4096) read no pi and are left out.
   learner  bench.py's C1, eager and graph launch: Run(20) + Modularity() + Run(20) leaves the checkpoint buffers Run(40)
            leaves; the result equals the statement over the learner's pi copied to the host.
   cpp      tests/cpp/modularity_test.cc and ammsb_main --modularity-out: each file equals, byte for byte,
@@ -54,6 +60,10 @@ def test_a_partition_gives_the_quality_counts_shifted_and_newmans_modularity():
 
 def test_planted_cover_scores_above_chance_within_the_derived_bound():
     _run(["planted"], "planted ok", 180)
+
+
+def test_pi_past_element_2_32_in_both_forms():
+    _run(["big"], "big ok", 300)
 
 
 @pytest.mark.parametrize("graph", [0, 1])

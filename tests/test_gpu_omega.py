@@ -16,6 +16,12 @@ One child process per group (omega_child.py):
   forms    every kernel form named and reached on both sides of its dispatch boundary; a misaligned pi takes the generic
            form and writes the same words; the identity universe.
   persistent  n = 3000 at K = 64, G = 64 (300 tiles), and n = 4200 (561 tiles, more than the grid's 512 blocks).
+  big      pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, 17 GB, zero but 640
+           planted rows in four windows that straddle byte offset 2^32, element 2^31 and element 2^32): detected bits of
+           the 640 planted rows and of the last window alone, as omega_bits_fast and, from a base 4 bytes past a 16-byte
+           boundary, as omega_bits_generic; truth bits and pairs against a ground truth with members >= N (skipped) and
+           members in zero rows (outside).  The inputs are first shown to tell a wrapped 32-bit offset apart in every
+           figure that reads pi.
   learner  Learner.CoverOmega on bench.py's C1 after 30 steps (eager and graph launch) with hostlib.generate_cover as
            the truth, over a universe of 2000 nodes and "covered", against the statement over the checkpointed pi;
            Run(20) + the call + Run(20) leaves the checkpoint buffers Run(40) leaves.  No recovery score is asserted:
@@ -50,6 +56,10 @@ def test_every_kernel_form_is_named_and_reached():
 
 def test_tiles_through_the_persistent_loop():
     _run(["persistent"], "persistent ok", 120)
+
+
+def test_pi_past_element_2_32_in_both_forms():
+    _run(["big"], "big ok", 300)
 
 
 @pytest.mark.parametrize("graph", [0, 1])

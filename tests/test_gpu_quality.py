@@ -15,7 +15,8 @@ One child process per group (quality_child.py):
   layout   pi as one, two and eleven-plus-a-ragged-one blocks; a misaligned block base takes the generic mask form at
            K = 256 and writes the fast form's bytes.
   forms    every mask and edges form is named and reached.
-  big      K = 8192 beyond 2^32 elements (17 GB), members and edges among the last rows.
+  big      K = 8192 beyond 2^32 elements (17 GB, zeroed), members and edges among the last rows; again from a base 4
+           bytes past a 16-byte boundary: quality_mask_generic, the same mask and counts.
   learner  Learner.CommunityQuality / SharedCommunities on bench.py's C1 after 30 steps (eager and graph launch) over
            the checkpointed pi; size equals CommunitySizes; Run(20) + the calls + Run(20) leaves the checkpoint buffers
            Run(40) leaves.

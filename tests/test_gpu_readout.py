@@ -11,7 +11,8 @@ One child process per group (readout_child.py):
            accumulated across the calls; a node list in descending order with repeats.
   ties     uniform rows, a whole row at the floor 1e-24, the maximum repeated inside one lane, across lanes and across
            256-column pieces, more holders of the maximum than T.
-  big      K = 8192 and a little over 2^32 elements in one block: the last 4096 rows, a node list and sizes.
+  big      K = 8192 and a little over 2^32 elements in one block: the last 4096 rows, a node list and sizes; again from a
+           base 4 bytes past a 16-byte boundary: readout_generic, the same outputs.
   learner  Learner.Memberships / CommunitySizes / Communities on bench.py's C1 after 30 steps (eager and graph launch);
            slabs; Run(20) + read-out + Run(20) leaves the checkpoint buffers Run(40) leaves.
   cpp      tests/cpp/readout_test.cc (mcmc::Learner::Memberships against GetPiRow), its memberships and communities file

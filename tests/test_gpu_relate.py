@@ -17,6 +17,12 @@ One child process per group (relate_child.py):
            the generic form and writes the same words.
   planted  two identical columns (Jaccard exactly 1, each the other's first partner); a strict subset (inside == 1.0 on
            one side, contained == 1.0 on the other); disjoint columns without a partner; ties to the lower id.
+  big      pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, 17 GB, zero but 640
+           planted rows in four windows that straddle byte offset 2^32, element 2^31 and element 2^32): bits of all rows
+           and of the slab that begins 128 rows before element 2^32, as relate_bits_fast and, from a base 4 bytes past a
+           16-byte boundary, as relate_bits_generic; the words of the planted rows equal the statement's, every other word
+           is 0, both forms equal; overlap, its diagonal and the partners of the full bits.  The inputs are first shown
+           to tell a wrapped 32-bit offset apart in every figure compared.
   learner  bench.py's C1 after 30 steps (eager and graph launch): RelatedCommunities and CommunityOverlap against the
            statement over the checkpointed pi; a max_bytes that forces many slabs gives the same tensors; Run(20) + the
            calls + Run(20) leaves the checkpoint buffers Run(40) leaves.  No property of the fitted cover is asserted:
@@ -51,6 +57,10 @@ def test_every_kernel_form_is_named_and_reached():
 
 def test_planted_duplicates_subsets_disjoint_columns_and_ties():
     _run(["planted"], "planted ok", 120)
+
+
+def test_pi_past_element_2_32_in_both_forms():
+    _run(["big"], "big ok", 300)
 
 
 @pytest.mark.parametrize("graph", [0, 1])

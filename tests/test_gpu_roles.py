@@ -17,6 +17,14 @@ One child process per group (roles_child.py):
            CommunityQuality.internal, kmembers == CommunitySizes, the sum of embedded == 2 (links - uncovered).
   planted  hostlib's planted graph and cover at N = 10^4 with pi set to the planted memberships: equal to the statement,
            misplaced() included; the mean embeddedness is larger than with the graph's node ids permuted (a sign).
+  big      pi past element 2^32 (postfit_support.big_pi: 2^19 + 128 rows of K = 8192 in one block, 17 GB, zero but 640
+           planted rows in four windows that straddle byte offset 2^32, element 2^31 and element 2^32): run() over the
+           adjacency of the keys of connect's big group, the mask as connect_mask_fast and, from a base 4 bytes past a
+           16-byte boundary, as connect_mask_generic; one state from one call equals one from two calls cut 128 rows
+           before element 2^32; every per-node array equals the statement on the planted rows and is 0 (home: -1)
+           elsewhere, the K-sized sums and counts are equal (roles_nodes_w2).  The inputs are first shown to tell a
+           wrapped 32-bit offset apart in every figure that reads pi.  roles_nodes_w1 (K <= 4096) reads no pi and is left
+           out.
   learner  bench.py's C1, eager and graph launch: Run(20) + NodeRoles() + Run(20) leaves the checkpoint buffers Run(40)
            leaves; the result equals the statement over the learner's pi and training_csr(); a node range.
   cpp      tests/cpp/roles_test.cc and ammsb_main --node-roles-out: each file equals, byte for byte, write_roles of the
@@ -48,6 +56,10 @@ def test_degrees_diagonal_sizes_and_coverage_agree_with_the_other_analyses():
 
 def test_planted_cover_equals_the_statement_and_is_more_embedded_than_a_permuted_graph():
     _run(["planted"], "planted ok", 180)
+
+
+def test_pi_past_element_2_32_in_both_forms():
+    _run(["big"], "big ok", 300)
 
 
 @pytest.mark.parametrize("graph", [0, 1])

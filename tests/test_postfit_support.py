@@ -105,3 +105,66 @@ def test_run_group_fails_without_a_device(monkeypatch, tmp_path):
     child.write_text("print('marker ok')\nprint('group ok')\n")
     with pytest.raises(pytest.fail.Exception, match="HIP device"):
         ps.run_group(str(child), [], "marker ok", 60)
+
+
+def test_big_fixture_windows_positions_aliases_and_keys():
+    """the pure part of the big-pi fixture: where the windows lie, the compact numbering, the row a wrapped offset reads,
+    and the edge list over them"""
+    import numpy as np
+    n, K = ps.BIG_ROWS, ps.BIG_K
+    ids, wins = ps.big_ids(), ps.big_windows()
+    assert n * K == 2 ** 32 + 2 ** 20 and ids.size == 640 == sum(hi - lo for lo, hi in wins) and (np.diff(ids) > 0).all()
+    assert ids[0] == 0 and ids[-1] == n - 1 and all(lo % 64 == 0 and hi % 64 == 0 for lo, hi in wins)
+    # what each window straddles: byte offset 2^32, element 2^31, element 2^32
+    assert [(lo * K < at <= (hi - 1) * K) for (lo, hi), at in zip(wins[1:], (2 ** 30, 2 ** 31, 2 ** 32))] == [True] * 3
+    assert (wins[1][0] + 64) * K * 4 == 2 ** 32 and (wins[2][0] + 64) * K == 2 ** 31 and (wins[3][0] + 128) * K == 2 ** 32
+    # the alias of a row: itself below 2^19, a row of the first window from there on, all 128 of them
+    assert np.array_equal(ps.big_alias(ids[ids < 2 ** 19]), ids[ids < 2 ** 19])
+    assert np.array_equal(ps.big_alias(ids[ids >= 2 ** 19]), np.arange(128)) and (ids >= 2 ** 19).sum() == 128
+    assert ps.big_alias(2 ** 19 + 5, K=4096) == 2 ** 19 + 5 and ps.big_alias(2 ** 20 + 5, K=4096) == 5
+    # positions: the planted rows in order, the zero rows after them, rows past the end stay past the end
+    assert np.array_equal(ps.big_positions(ids), np.arange(640))
+    assert np.array_equal(ps.big_positions(ids[::-7]), np.arange(640)[::-7])
+    zr = ps.BIG_ZERO_ROWS
+    assert not set(zr) & set(ids.tolist()) and all(z < n for z in zr)
+    assert ps.big_positions(list(zr)).tolist() == [640 + j for j in range(len(zr))]
+    past = ps.big_positions([n, n + 5, 2 ** 32 - 1])
+    assert (past >= 640 + len(zr)).all() and (past < 2 ** 32).all() and len(set(past.tolist())) == 3
+    with pytest.raises(ValueError):
+        ps.big_positions([129])
+    # the wrapped view of the compact rows: only the rows >= 2^19 change, each to its alias's row
+    compact = np.arange(640 * 3, dtype=np.float32).reshape(640, 3) + 1
+    wrapped = ps.big_wrapped(compact)
+    assert np.array_equal(wrapped[:512], compact[:512]) and np.array_equal(wrapped[512:], compact[:128])
+    ext = ps.big_extended(compact)
+    assert ext.shape == (640 + len(zr), 3) and not ext[640:].any() and np.array_equal(ext[:640], compact)
+    assert ps.big_threshold(np.linspace(0.001, 1, 640 * 100, dtype=np.float32).reshape(640, 100)) > 0
+    # the keys: every two windows and every window with itself, both orders, the irregular ones, the zero rows
+    keys = ps.big_keys(3)
+    assert np.array_equal(keys, ps.big_keys(3)) and 2000 < keys.size < 10000
+    a, b = (keys >> np.uint64(32)).astype(np.int64), (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    win_of = lambda r: np.select([(r >= lo) & (r < hi) for lo, hi in wins], range(4), -1)   # noqa: E731
+    valid = (a < n) & (b < n)
+    seen = {(int(x), int(y)) for x, y in zip(win_of(a)[valid], win_of(b)[valid])}
+    assert {(i, j) for i in range(4) for j in range(4)} <= seen
+    assert ((a >= 2 ** 19) & (b >= 2 ** 19) & valid).sum() > 20 and ((a >= 2 ** 19) & (b < 128)).sum() > 20
+    assert (a == b).sum() > 20 and (~valid).sum() > 20 and np.unique(keys).size < keys.size - 20
+    assert (a == n).any() or (b == n).any()
+    assert all(((a == z) | (b == z)).sum() >= 4 for z in zr) and (np.isin(a, zr) & np.isin(b, zr)).any()
+    local = ps.big_remap(keys)
+    la, lb = (local >> np.uint64(32)).astype(np.int64), (local & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    Nc = 640 + len(zr)
+    assert np.array_equal((la < Nc) & (lb < Nc), valid) and np.array_equal(la < Nc, a < n) and np.array_equal(lb < Nc, b < n)
+    assert np.array_equal(la[a < n], ps.big_positions(a[a < n])) and np.array_equal(la == lb, a == b)
+    # the adjacency of the keys, globally and in compact numbering: the same rows
+    off, tgt = ps.big_csr(keys, n)
+    loff, ltgt = ps.big_csr(local, Nc)
+    assert off.size == n + 1 and int(off[-1]) == tgt.size == int((a < n).sum() + (b < n).sum()) == int(loff[-1])
+    rows = np.concatenate([ids, zr])
+    assert np.array_equal(np.diff(off.astype(np.int64))[rows], np.diff(loff.astype(np.int64)))
+    assert int(np.diff(off.astype(np.int64))[rows].sum()) == tgt.size        # no other row has a target
+    for g, c in ((0, 0), (int(ids[-1]), 639), (zr[1], 641)):
+        mine = tgt[int(off[g]):int(off[g + 1])].astype(np.int64)
+        theirs = ltgt[int(loff[c]):int(loff[c + 1])].astype(np.int64)
+        assert mine.size and np.array_equal(ps.big_positions(mine), theirs)
+    assert (tgt.astype(np.int64) >= n).any()
