@@ -249,6 +249,29 @@ class Learner {
   bool WriteNodeRoles(std::ostream* out, Float threshold, uint32_t top = 4, const std::string& among = "all",
                       uint32_t min_count = 0, const std::vector<Edge>* edges = nullptr);
 
+  // Do the communities hold triangles?  Over the simple adjacency of `edges` (nullptr: every training link once; else the
+  // keys (a << 32) | b: both directions of every key with both ends < N, each row sorted and made unique, loops removed; a
+  // key with an end >= N counted in skipped, repeats and loops in dropped) the integers of include/ammsb_triangles.h for
+  // the cover pi[a, k] >= threshold: per node degree, tri, tri_in, tri_comms, per community ktri3, kpart, and from one run
+  // of the node roles without a selection over the same rows kmembers and wedges = (ksq - ksum) / 2, all exact.  Derive()
+  // is the header's float64 statement over them.  std::invalid_argument on a bad threshold or a row of more than 65535
+  // targets.  Waits, reads and perturbs like CommunityQuality.
+  struct TrianglesResult {
+    std::vector<uint32_t> degree, tri, tri_in, tri_comms;  // [N]
+    std::vector<uint64_t> ktri3, kpart, kmembers, wedges;   // [K]
+    uint64_t M = 0, skipped = 0, dropped = 0;               // targets of the simple adjacency; keys left out
+    std::vector<double> tpr, clustering;                    // [K], -1 where not defined
+    std::vector<uint64_t> triangles;                        // [K]
+    std::vector<double> local_clustering, inside;           // [N], -1 where not defined
+    uint64_t total = 0;
+    double transitivity = -1, avg_clustering = -1;
+    void Derive();  // std::logic_error where 3 does not divide a count over all nodes
+  };
+  void Triangles(Float threshold, const std::vector<Edge>* edges, TrianglesResult* result);
+  // `# N K M threshold skipped dropped total`, `c k members part tri3 wedges` per community, `n a degree tri tri_in
+  // tri_comms` per node: integers throughout.
+  bool WriteTriangles(std::ostream* out, Float threshold, const std::vector<Edge>* edges = nullptr);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

@@ -77,7 +77,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy, modularityOut, rolesOut, rolesAmong = "all";
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy, modularityOut, rolesOut, rolesAmong = "all", trianglesOut;
   bool haveCoverThreshold = false;
   double coverThreshold = 0.05;
   bool haveRelatedThreshold = false, haveRelatedTop = false;
@@ -92,6 +92,8 @@ int main(int argc, char** argv) {
   bool haveRolesThreshold = false, haveRolesTop = false, haveRolesAmong = false;
   double rolesThreshold = 0.05;
   long rolesTop = 4;
+  bool haveTrianglesThreshold = false;
+  double trianglesThreshold = 0.05;
   bool haveQualityThreshold = false;
   double qualityThreshold = 0.05;
   bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
@@ -272,6 +274,14 @@ int main(int argc, char** argv) {
                rolesAmong = v;
                return true;
              }},
+      OptStr("triangles-out", 0, &trianglesOut),  // (new) after the last perplexity line: `# N K M threshold skipped dropped total`, `c k members part tri3 wedges` per community, `n a degree tri tri_in tri_comms` per node: the triangles of the training adjacency inside the detected communities
+      Option{"triangles-threshold", 0, "0.05 (new, with --triangles-out: a node is a member of k iff pi[a, k] >= it)",
+             [&](const std::string& v) {
+               haveTrianglesThreshold = true;
+               std::istringstream in(v);
+               in >> trianglesThreshold;
+               return !in.fail() && in.eof();
+             }},
       OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
       Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
              [&](const std::string& v) {
@@ -389,6 +399,9 @@ int main(int argc, char** argv) {
     Fatal("--node-roles-threshold must be finite and >= 0");
   if (rolesTop < 1 || rolesTop > 16) Fatal("--node-roles-top must be in 1..16");
   if (rolesAmong != "all" && rolesAmong != "own") Fatal("--node-roles-among must be all or own");
+  if (haveTrianglesThreshold && trianglesOut.empty()) Fatal("--triangles-threshold needs --triangles-out FILE");
+  if (!(trianglesThreshold >= 0) || !std::isfinite(static_cast<float>(trianglesThreshold)))
+    Fatal("--triangles-threshold must be finite and >= 0");
   if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
     Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
   if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
@@ -640,6 +653,18 @@ int main(int argc, char** argv) {
       }
     } catch (const std::exception& e) {
       Fatal(std::string("node roles: ") + e.what());
+    }
+  }
+  if (!trianglesOut.empty()) {
+    // every rank holds all of pi and the training links: the read-out is local, rank 0's file is the answer
+    try {
+      if (rank == 0) {
+        std::ofstream out(trianglesOut);
+        if (!out.good() || !learner.WriteTriangles(&out, static_cast<mcmc::Float>(trianglesThreshold)))
+          Fatal("cannot write triangles " + trianglesOut);
+      }
+    } catch (const std::exception& e) {
+      Fatal(std::string("triangles: ") + e.what());
     }
   }
   learner.PrintStats();

@@ -1,8 +1,8 @@
 // mcmc::Learner's post-fit analyses (include/mcmc/learner.h): what reads a fitted model out -- memberships and
 // communities, link prediction, link communities, community quality, the three comparisons with a ground-truth cover
 // (F1 match, overlapping NMI, Omega index), how the detected communities relate to each other, how they are linked, the
-// overlapping modularity of the cover and the role of every node in it.  Each is
-// a thin driver of one library of its own (libammsb_readout.so ... libammsb_roles.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
+// overlapping modularity of the cover, the role of every node in it and the triangles inside the communities.  Each is
+// a thin driver of one library of its own (libammsb_readout.so ... libammsb_triangles.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
 // read the results back, and for the Write* methods print them.  Nothing here touches the training loop of learner.cc.
 #include "mcmc/learner.h"
 #include "ammsb_readout.h"
@@ -16,6 +16,7 @@
 #include "ammsb_connect.h"
 #include "ammsb_modularity.h"
 #include "ammsb_roles.h"
+#include "ammsb_triangles.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1126,6 +1127,145 @@ bool Learner::WriteNodeRoles(std::ostream* out, Float threshold, uint32_t top, c
       *out << " " << r.home[a * top + j] << " " << r.hcount[a * top + j] << " " << ((r.hflags[a] >> j) & 1u);
     *out << "\n";
   }
+  return static_cast<bool>(*out);
+}
+
+// ---- do the communities hold triangles: libammsb_triangles.so and libammsb_roles.so over libammsb_connect.so's mask of pi
+// and one simple CSR adjacency
+void Learner::TrianglesResult::Derive() {
+#pragma STDC FP_CONTRACT OFF
+  const size_t n = degree.size(), K = ktri3.size();
+  // (every integer is converted once, to nearest even)
+  uint64_t sum_tri = 0, all_pairs = 0;
+  for (size_t i = 0; i < n; ++i) sum_tri += tri[i];
+  if (sum_tri % 3) throw std::logic_error("Triangles: the nodes' triangles are not a multiple of 3");
+  tpr.assign(K, -1.0);
+  clustering.assign(K, -1.0);
+  triangles.assign(K, 0);
+  for (size_t k = 0; k < K; ++k) {
+    if (ktri3[k] % 3) throw std::logic_error("Triangles: ktri3 is not a multiple of 3");
+    triangles[k] = ktri3[k] / 3;
+    if (kmembers[k] > 0) tpr[k] = static_cast<double>(kpart[k]) / static_cast<double>(kmembers[k]);
+    if (wedges[k] > 0) clustering[k] = static_cast<double>(ktri3[k]) / static_cast<double>(wedges[k]);
+  }
+  local_clustering.assign(n, -1.0);
+  inside.assign(n, -1.0);
+  double sum_local = 0;
+  uint64_t some = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (degree[i] >= 2) {
+      const double d = static_cast<double>(degree[i]);
+      const double less = d - 1.0;
+      const double product = d * less;
+      const double pairs = product / 2.0;
+      local_clustering[i] = static_cast<double>(tri[i]) / pairs;
+      sum_local += local_clustering[i];
+      ++some;
+      all_pairs += static_cast<uint64_t>(degree[i]) * (degree[i] - 1) / 2;
+    }
+    if (tri[i] > 0) inside[i] = static_cast<double>(tri_in[i]) / static_cast<double>(tri[i]);
+  }
+  total = sum_tri / 3;
+  transitivity = all_pairs ? static_cast<double>(sum_tri) / static_cast<double>(all_pairs) : -1.0;
+  avg_clustering = some ? sum_local / static_cast<double>(some) : -1.0;
+}
+
+void Learner::Triangles(Float threshold, const std::vector<Edge>* edges, TrianglesResult* result) {
+  CheckThreshold("Triangles", threshold);
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  if (K == 0 || K > AMMSB_TRIANGLES_MAX_COLS) throw std::runtime_error("Triangles: K outside 1..8192");
+  // the simple adjacency: both directions of every valid key, each row sorted and made unique, loops left out
+  const std::vector<Edge> training = edges ? std::vector<Edge>() : SortedTrainingLinks(cfg_);
+  const std::vector<Edge>& list = edges ? *edges : training;
+  std::vector<std::vector<Vertex>> rows(N);
+  uint64_t valid = 0, lost = 0;  // keys with both ends < N; with an end >= N
+  for (Edge e : list) {
+    const uint64_t a = e >> 32, b = e & 0xFFFFFFFFull;
+    if (a >= N || b >= N) {
+      ++lost;
+      continue;
+    }
+    ++valid;
+    if (a == b) continue;
+    rows[a].push_back(static_cast<Vertex>(b));
+    rows[b].push_back(static_cast<Vertex>(a));
+  }
+  std::vector<uint64_t> offsets(N + 1, 0);
+  std::vector<Vertex> targets;
+  for (uint64_t a = 0; a < N; ++a) {
+    std::sort(rows[a].begin(), rows[a].end());
+    rows[a].erase(std::unique(rows[a].begin(), rows[a].end()), rows[a].end());
+    if (rows[a].size() > AMMSB_TRIANGLES_MAX_ROW) throw std::invalid_argument("Triangles: a row of more than 65535 targets");
+    targets.insert(targets.end(), rows[a].begin(), rows[a].end());
+    offsets[a + 1] = targets.size();
+    std::vector<Vertex>().swap(rows[a]);
+  }
+  TrianglesResult& r = *result;
+  r.M = targets.size();
+  r.skipped = lost;
+  r.dropped = valid - r.M / 2;
+  r.degree.assign(N, 0);
+  r.tri.assign(N, 0);
+  r.tri_in.assign(N, 0);
+  r.tri_comms.assign(N, 0);
+  r.ktri3.assign(K, 0);
+  r.kpart.assign(K, 0);
+  r.kmembers.assign(K, 0);
+  r.wedges.assign(K, 0);
+  if (N > 0) {
+    hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
+    const clcuda::Context context = queue_.GetContext();
+    const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
+    if (targets.empty()) targets.push_back(0);  // (a buffer needs a byte; no offset reaches it)
+    // ktri3 kpart counts, then the node roles' ksum ksq kmembers counts; votes squares
+    clcuda::Buffer<uint64_t> d_mask(context, words), d_sums(context, 5 * K + 4), d_wide(context, 2 * N);
+    clcuda::Buffer<uint32_t> d_node(context, 7 * N);  // tri tri_in tri_comms; degree own embedded reached
+    clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
+    clcuda::Buffer<Vertex> d_targets(context, queue_, targets.begin(), targets.end());
+    const hipError_t e = hipMemsetAsync(d_sums(), 0, (5 * K + 4) * sizeof(uint64_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("Triangles: memset: ") + hipGetErrorString(e));
+    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
+    rc = ammsb_triangles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N, d_node(), d_node() + N,
+                               d_node() + 2 * N, d_sums(), d_sums() + K, d_sums() + 2 * K, stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_triangles_nodes", rc, ammsb_triangles_last_error());
+    uint64_t* const roles = d_sums() + 2 * K + 2;
+    rc = ammsb_roles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N, AMMSB_ROLES_ALL, 0, 0,
+                           d_node() + 3 * N, d_node() + 4 * N, d_node() + 5 * N, d_node() + 6 * N, d_wide(), d_wide() + N,
+                           nullptr, nullptr, nullptr, roles, roles + K, roles + 2 * K, roles + 3 * K, stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_roles_nodes", rc, ammsb_roles_last_error());
+    std::vector<uint64_t> sums(5 * K + 4);
+    std::vector<uint32_t> node(4 * N);
+    d_sums.Read(queue_, 5 * K + 4, sums.data());
+    d_node.Read(queue_, 4 * N, node.data());
+    queue_.Finish();
+    r.tri.assign(node.begin(), node.begin() + N);
+    r.tri_in.assign(node.begin() + N, node.begin() + 2 * N);
+    r.tri_comms.assign(node.begin() + 2 * N, node.begin() + 3 * N);
+    r.degree.assign(node.begin() + 3 * N, node.end());
+    r.ktri3.assign(sums.begin(), sums.begin() + K);
+    r.kpart.assign(sums.begin() + K, sums.begin() + 2 * K);
+    const uint64_t* ksum = sums.data() + 2 * K + 2;
+    for (uint64_t k = 0; k < K; ++k) {
+      r.wedges[k] = (ksum[K + k] - ksum[k]) / 2;
+      r.kmembers[k] = ksum[2 * K + k];
+    }
+    if (sums[2 * K + 1] != 0) throw std::runtime_error("Triangles: the simple adjacency holds a target >= N");
+  }
+  r.Derive();
+}
+
+bool Learner::WriteTriangles(std::ostream* out, Float threshold, const std::vector<Edge>* edges) {
+  TrianglesResult r;
+  Triangles(threshold, edges, &r);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.M << " " << G9(threshold) << " " << r.skipped << " " << r.dropped
+       << " " << r.total << "\n";
+  for (size_t k = 0; k < r.ktri3.size(); ++k)
+    *out << "c " << k << " " << r.kmembers[k] << " " << r.kpart[k] << " " << r.ktri3[k] << " " << r.wedges[k] << "\n";
+  for (size_t a = 0; a < r.degree.size(); ++a)
+    *out << "n " << a << " " << r.degree[a] << " " << r.tri[a] << " " << r.tri_in[a] << " " << r.tri_comms[a] << "\n";
   return static_cast<bool>(*out);
 }
 

@@ -1476,6 +1476,93 @@ class NodeRoles:
         return self.rl.last_kernel_name()
 
 
+class Triangles:
+    """The triangles inside the detected communities (include/ammsb_triangles.h): over CommunityLinks' node-major
+    membership bits and a simple CSR adjacency, a wave per node intersects the node's sorted row with its neighbours' rows
+    and counts the node's triangles, those whose corners share a community, and per community the triangles inside it
+    (three times) and the members that are a corner of one.  Integer adds and compares: exact, and independent of the
+    kernel form and of how the node range is cut into calls.  Owns nothing but the tensors it returns."""
+
+    PER_NODE = ("tri", "tri_in", "tri_comms")
+    PER_COMMUNITY = ("ktri3", "kpart")
+
+    def __init__(self, ctx):
+        from . import _triangles
+        self.ctx = ctx
+        self.tr = _triangles
+        self.lib = _triangles.load()
+        self.links = CommunityLinks(ctx)
+
+    def state(self, N, K):
+        """-> the zeroed outputs of nodes() for an N x K pi: name -> device tensor (uint32 as int32, uint64 as int64); tri,
+        tri_in, tri_comms [N]; ktri3, kpart [K]; counts [2] (the sum of tri, targets >= N)"""
+        out = {name: self.ctx.zeros((N,), torch.int32) for name in self.PER_NODE}
+        for name in self.PER_COMMUNITY:
+            out[name] = self.ctx.zeros((K,), torch.int64)
+        out["counts"] = self.ctx.zeros((2,), torch.int64)
+        return out
+
+    def verify(self, N, offsets, targets):
+        """the rows are what the header asks of them, as far as a few statements can tell: offsets ascend inside
+        targets, and every row is strictly ascending, holds no loop and no target >= N (symmetry is the caller's).  Waits
+        for the answer -> the longest row"""
+        if not N:
+            return 0
+        lengths = offsets[1:] - offsets[:-1]
+        lo, hi = int(offsets[0]), int(offsets[-1])
+        if lo < 0 or hi > targets.numel() or int(lengths.min()) < 0:
+            raise AmmsbError("triangles: the offsets do not ascend inside the targets")
+        t = targets[lo:hi].to(torch.int64) & 0xFFFFFFFF
+        src = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=t.device), lengths)
+        if bool((t >= N).any()):
+            raise AmmsbError("triangles: a target is not below N = %d" % N)
+        if bool((t == src).any()):
+            raise AmmsbError("triangles: a row holds its own node")
+        if bool(((src[1:] == src[:-1]) & (t[1:] <= t[:-1])).any()):
+            raise AmmsbError("triangles: a row is not strictly ascending")
+        return self.tr.check_rows(int(lengths.max()))
+
+    def nodes(self, mask, N, K, offsets, targets, first=0, count=None, state=None):
+        """mask: what CommunityLinks.mask() returned for an N x K pi; offsets [N + 1] int64 (uint64 bits) and targets int32
+        (uint32 bits): contiguous device tensors, the simple CSR of the header, which is verified on the device before
+        anything is launched.  Handles the nodes first .. first + count - 1 (default: through N - 1) into `state`, which is
+        made and zeroed where none is given; calls over disjoint ranges fill one state -> state"""
+        N, K = int(N), int(K)
+        first, count = self.tr.check_nodes((first, N - int(first) if count is None else count), N)
+        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
+            raise AmmsbError("triangles: not the mask of a %d x %d pi" % (N, K))
+        if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() != N + 1:
+            raise AmmsbError("triangles: offsets must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
+        if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 1:
+            raise AmmsbError("triangles: targets must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        self.verify(N, offsets, targets)
+        if state is None:
+            state = self.state(N, K)
+        for name in self.PER_NODE:
+            t = state[name]
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != N:
+                raise AmmsbError("triangles: %s of the state does not fit N = %d" % (name, N))
+        for name in self.PER_COMMUNITY + ("counts",):
+            t = state[name]
+            if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != (2 if name == "counts" else K):
+                raise AmmsbError("triangles: %s of the state does not fit K = %d" % (name, K))
+        if count:  # (an empty range is a valid no-op; an empty tensor has no address)
+            # an adjacency without a target still needs an address for `targets`: the offsets are read, no target is
+            tgt = targets if targets.numel() else self.ctx.zeros((1,), torch.int32)
+            self.tr.check(self.lib.ammsb_triangles_nodes(
+                _ptr(mask), N, K, _ptr(offsets), _ptr(tgt), first, count, _ptr(state["tri"]), _ptr(state["tri_in"]),
+                _ptr(state["tri_comms"]), _ptr(state["ktri3"]), _ptr(state["kpart"]), _ptr(state["counts"]), _stream()))
+        return state
+
+    def run(self, pi, thr, offsets, targets, first=0, count=None):
+        """-> the state of nodes() for the cover (pi, thr) and the simple CSR"""
+        N, K = int(pi.desc.num_rows), int(pi.cols)
+        return self.nodes(self.links.mask(pi, self.tr.check_threshold(thr)), N, K, offsets, targets, first=first, count=count)
+
+    def kernel_name(self):
+        return self.tr.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

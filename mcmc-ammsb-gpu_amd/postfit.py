@@ -1,6 +1,6 @@
 """The post-fit analyses of a Learner: what reads a fitted model out -- memberships and communities, link prediction,
 link communities, community quality, the three comparisons with a ground-truth cover (F1 match, overlapping NMI, Omega
-index), how the detected communities relate to each other, how they are linked, the overlapping modularity of the cover and the role of every node in it.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
+index), how the detected communities relate to each other, how they are linked, the overlapping modularity of the cover, the role of every node in it and the triangles inside the communities.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
 holds all of pi, so none is a collective), and nothing of the iteration is touched -- no RNG stream, no counter, no
 buffer.  There is no CPU path: without a device every one of them raises."""
 import numpy as np
@@ -490,3 +490,65 @@ class PostFit:
                             part("squares", np.uint64), part("home", np.int32), part("hcount", np.uint32),
                             part("hflags", np.uint32), whole("ksum"), whole("ksq"), whole("kmembers"), valid, skipped + lost,
                             N=self.cfg.N, first=first)
+
+    # ---- do the communities hold triangles? (include/ammsb_triangles.h)
+    def _triangles(self):
+        return self._postfit_op("_triangles_op", "Triangles", "the triangles")
+
+    def _simple_csr(self, edges):
+        """keys (a << 32) | b, or None for the training links -> (offsets [N + 1] int64, targets int32, M, skipped,
+        dropped): the simple symmetric adjacency of the list, built on the device -- both directions of every key with both
+        ends < N as 64-bit keys, sorted, made unique, loops removed; skipped counts the keys with an end >= N, dropped the
+        repeats (in either order) and loops.  That of the training links is built once and kept."""
+        from . import _triangles
+        if edges is None and getattr(self, "_training_simple_csr", None) is not None:
+            return self._training_simple_csr
+        N = self.cfg.N
+        if N >= 2 ** 31:
+            raise AmmsbError("triangles: the simplification sorts signed 64-bit keys and takes N < 2^31")
+        keys = self._linkcomm_edges(edges)
+        if keys.dtype != torch.int64 or keys.dim() != 1:
+            raise AmmsbError("triangles: edges must be 1-d uint64 keys (a << 32) | b")
+        a, b = (keys >> 32) & 0xFFFFFFFF, keys & 0xFFFFFFFF
+        ok = (a < N) & (b < N)
+        a, b = a[ok], b[ok]
+        both = torch.unique(torch.cat(((a << 32) | b, (b << 32) | a)))   # (sorted)
+        both = both[(both >> 32) != (both & 0xFFFFFFFF)]
+        src = both >> 32
+        rows = torch.bincount(src, minlength=N)
+        _triangles.check_rows(int(rows.max()) if N else 0)
+        offsets = torch.zeros(N + 1, dtype=torch.int64, device=keys.device)
+        offsets[1:] = torch.cumsum(rows, 0)
+        M = int(both.numel())
+        out = (offsets, (both & 0xFFFFFFFF).to(torch.int32).contiguous(), M, int(keys.numel() - a.numel()),
+               int(a.numel()) - M // 2)
+        if edges is None:
+            self._training_simple_csr = out
+        return out
+
+    def Triangles(self, threshold=0.05, edges=None, nodes=None):
+        """-> _triangles.Triangles: the triangles of every node (or of the range nodes=(first, count)) and of every
+        community of the cover pi[a, k] >= threshold in a simple adjacency: that of the training links (edges=None), or
+        that of `edges` (host array or device tensor of (a << 32) | b; repeats and loops counted in .dropped, a key with an
+        end >= N in .skipped).  .degree, .tri, .tri_in (the triangles whose three corners share a community), .tri_comms
+        per node; .ktri3 (three times the triangles inside k), .kpart (the members that are a corner of one), .kmembers,
+        .wedges per community, all exact integers; .tpr, .triangles, .clustering [K], .local_clustering, .inside [n],
+        .total, .transitivity, .avg_clustering on the host; .without_triangles().  A row of more than 65535 targets is
+        refused."""
+        from . import _triangles
+        threshold = _triangles.check_threshold(threshold)
+        first, count = _triangles.check_nodes(nodes, self.cfg.N)
+        op, roles = self._triangles(), self._roles()
+        self.drain()
+        offsets, targets, M, skipped, dropped = self._simple_csr(edges)
+        N, K = self.cfg.N, int(self.pi.cols)
+        mask = op.links.mask(self.pi, threshold)
+        st = op.nodes(mask, N, K, offsets, targets, first=first, count=count)
+        # degree, kmembers and the wedges: the node roles without a selection over the same rows
+        rs = roles.nodes(mask, N, K, offsets, targets, first=first, count=count, top=0)
+        part = lambda s, name: s[name][first:first + count].cpu().numpy().view(np.uint32)   # noqa: E731
+        whole = lambda s, name: s[name].cpu().numpy().view(np.uint64)                       # noqa: E731
+        ksum, ksq = whole(rs, "ksum"), whole(rs, "ksq")
+        return _triangles.Triangles(threshold, part(rs, "degree"), part(st, "tri"), part(st, "tri_in"), part(st, "tri_comms"),
+                                    whole(st, "ktri3"), whole(st, "kpart"), whole(rs, "kmembers"), (ksq - ksum) // np.uint64(2),
+                                    M, skipped, dropped, N=N, first=first)
