@@ -69,6 +69,104 @@ bool FileExists(const std::string& f) {
   exit(2);
 }
 
+// A flag that modifies one post-fit output (new, as are all of them).  It knows whether it was given -- it then needs
+// its output's flag -- reads the whole of its argument ("4x" is invalid), and carries its own range rule.
+struct Modifier {
+  std::string name, help;
+  bool given = false;
+  Modifier(const std::string& n, const std::string& h) : name(n), help(h) {}
+  virtual ~Modifier() {}
+  virtual bool Set(const std::string& v) = 0;
+  virtual std::string MustBe() const = 0;  // the value's rule where the value breaks it ("in 1..16"), else ""
+  void Check() const {
+    const std::string rule = MustBe();
+    if (!rule.empty()) Fatal("--" + name + " must be " + rule);
+  }
+  Option AsOption() {
+    return Option{name, 0, help, [this](const std::string& v) {
+                    given = true;
+                    return Set(v);
+                  }};
+  }
+
+ protected:
+  template <class T>
+  static bool Parse(const std::string& v, T* x) {
+    std::istringstream in(v);
+    in >> *x;
+    return !in.fail() && in.eof();
+  }
+};
+
+// pi[a, k] >= value makes a a member of k.  The libraries take a binary32, so that is what has to be finite;
+// --membership-threshold alone (finite = false) keeps its older rule.
+struct Threshold : Modifier {
+  double value;
+  bool finite;
+  Threshold(const std::string& n, double def, const std::string& h, bool f = true) : Modifier(n, h), value(def), finite(f) {}
+  bool Set(const std::string& v) override { return Parse(v, &value); }
+  std::string MustBe() const override {
+    if (value >= 0 && (!finite || std::isfinite(static_cast<float>(value)))) return "";
+    return finite ? "finite and >= 0" : ">= 0";
+  }
+};
+
+// how many entries a row of the output keeps at the most
+struct Top : Modifier {
+  long value, max;
+  Top(const std::string& n, long def, long mx, const std::string& h) : Modifier(n, h), value(def), max(mx) {}
+  bool Set(const std::string& v) override { return Parse(v, &value); }
+  std::string MustBe() const override { return value < 1 || value > max ? "in 1.." + std::to_string(max) : ""; }
+};
+
+struct Count : Modifier {
+  long long value;
+  Count(const std::string& n, long long def, const std::string& h) : Modifier(n, h), value(def) {}
+  bool Set(const std::string& v) override { return Parse(v, &value); }
+  std::string MustBe() const override { return value < 0 ? ">= 0" : ""; }
+};
+
+// One of a few words.  The choices that --help shows no default for take an empty argument as not given.
+struct Choice : Modifier {
+  std::vector<std::string> words;
+  std::string def, value;
+  bool emptyIsDefault;
+  Choice(const std::string& n, const std::vector<std::string>& w, const std::string& d, const std::string& h = "")
+      : Modifier(n, h), words(w), def(d), emptyIsDefault(h.empty()) {}
+  bool Set(const std::string& v) override {
+    value = v;
+    given = !(emptyIsDefault && v.empty());
+    return true;
+  }
+  const std::string& Get() const { return given ? value : def; }
+  std::string MustBe() const override {
+    if (std::find(words.begin(), words.end(), Get()) != words.end()) return "";
+    std::string list;
+    for (size_t i = 0; i < words.size(); ++i) list += (i == 0 ? "" : i + 1 == words.size() ? " or " : ", ") + words[i];
+    return list;
+  }
+};
+
+struct Text : Modifier {
+  std::string value;
+  explicit Text(const std::string& n) : Modifier(n, "") {}
+  bool Set(const std::string& v) override {
+    value = v;
+    given = !v.empty();
+    return true;
+  }
+  std::string MustBe() const override { return ""; }
+};
+
+// One post-fit output: --FLAG FILE makes rank 0 write FILE after the last perplexity line.
+struct Output {
+  std::string flag;
+  std::string words;                 // "cannot write WORDS FILE", "WORDS: what the writer threw"
+  std::vector<Modifier*> modifiers;  // each of them needs --FLAG
+  std::function<bool(mcmc::Learner&, std::ostream*)> write;
+  std::string file = "";
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -77,33 +175,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < argc; ++i) s << argv[i] << " ";
     std::cerr << "I " << s.str() << std::endl;
   }
-  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, communitiesOut, linksOut, linksNodes, linksExclude, linkCommOut, qualityOut, groundTruth, coverMatchOut, coverNmiOut, coverOmegaOut, coverOmegaUniverse, relatedOut, relatedBy, linkedOut, linkedBy, modularityOut, rolesOut, rolesAmong = "all", trianglesOut;
-  bool haveCoverThreshold = false;
-  double coverThreshold = 0.05;
-  bool haveRelatedThreshold = false, haveRelatedTop = false;
-  double relatedThreshold = 0.05;
-  long relatedTop = 4;
-  bool haveLinkedThreshold = false, haveLinkedTop = false, haveLinkedMinLinks = false;
-  double linkedThreshold = 0.05;
-  long linkedTop = 4;
-  long long linkedMinLinks = 1;
-  bool haveModularityThreshold = false;
-  double modularityThreshold = 0.05;
-  bool haveRolesThreshold = false, haveRolesTop = false, haveRolesAmong = false;
-  double rolesThreshold = 0.05;
-  long rolesTop = 4;
-  bool haveTrianglesThreshold = false;
-  double trianglesThreshold = 0.05;
-  bool haveQualityThreshold = false;
-  double qualityThreshold = 0.05;
-  bool haveLinkCommTop = false, haveLinkCommMinTerm = false;
-  long linkCommTop = 1;
-  double linkCommMinTerm = 0;
-  bool haveLinksTop = false;
-  long linksTop = 10;
-  bool haveMembershipTop = false, haveMembershipThreshold = false;
-  long membershipTop = 4;
-  double membershipThreshold = 0;
+  std::string filename, loadFile, dumpFile, ckptIn, ckptOut, exchangeKind, groundTruth;
   int deviceId = -1;
   mcmc::Config cfg;
   uint32_t max_iters = 100;
@@ -170,143 +242,139 @@ int main(int argc, char** argv) {
       Opt("device", 0, &deviceId, "-1 (new: HIP device; default LOCAL_RANK with --exchange, else 0)"),
       OptStr("checkpoint-in", 0, &ckptIn),    // (new) Learner::Parse before the first iteration
       OptStr("checkpoint-out", 0, &ckptOut),  // (new) Learner::Serialize after the last one
-      OptStr("communities-out", 0, &communitiesOut),  // (new) after the last perplexity line: `# N K top threshold`, then `k size n0 n1 ...` per community
-      OptStr("link-communities-out", 0, &linkCommOut),  // (new) after the last perplexity line: `# N K E top min_term`, then `a b p n k0 t0 k1 t1 ...` per training link
-      Option{"link-communities-top", 0, "1 (new, with --link-communities-out: largest terms kept per link, 1..16)",
-             [&](const std::string& v) {
-               haveLinkCommTop = true;
-               std::istringstream in(v);
-               in >> linkCommTop;
-               return !in.fail() && in.eof();
-             }},
-      Option{"link-communities-min-term", 0, "0 (new, with --link-communities-out: terms below it take no slot)",
-             [&](const std::string& v) {
-               haveLinkCommMinTerm = true;
-               std::istringstream in(v);
-               in >> linkCommMinTerm;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("community-quality-out", 0, &qualityOut),  // (new) after the last perplexity line: `# N K E threshold uncovered`, then `k size internal boundary conductance density` per community
-      Option{"community-quality-threshold", 0, "0.05 (new, with --community-quality-out: a node is a member of k iff pi[a, k] >= it)",
-             [&](const std::string& v) {
-               haveQualityThreshold = true;
-               std::istringstream in(v);
-               in >> qualityThreshold;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("ground-truth", 0, &groundTruth),  // (new, with --cover-match-out) a SNAP cmty file: one community per line; the graph file's own ids with --file, dense ids with --load-data
-      OptStr("cover-match-out", 0, &coverMatchOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold skipped f1_truth f1_detected avg_f1`, then `t g size best overlap f1` per ground-truth and `d k size best overlap f1` per detected community
-      OptStr("cover-nmi-out", 0, &coverNmiOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold skipped nmi_lfk nmi_max`, then `t g size H h` per ground-truth and `d k size H h` per detected community (H the entropy, h the conditional entropy given the other cover; %.17g)
-      OptStr("cover-omega-out", 0, &coverOmegaOut),  // (new, with --ground-truth) after the last perplexity line: `# N K G threshold universe_n skipped outside omega omega_unadjusted`, then `j agree detected truth` per level: the pairs of the universe that share j communities (%.17g, `nan` where undefined)
-      OptStr("cover-omega-universe", 0, &coverOmegaUniverse),  // (new, with --cover-omega-out) covered (default: the nodes some ground-truth community holds) | all
-      Option{"cover-match-threshold", 0, "0.05 (new, with --ground-truth and --cover-match-out: a node is a member of k iff pi[a, k] >= it)",
-             [&](const std::string& v) {
-               haveCoverThreshold = true;
-               std::istringstream in(v);
-               in >> coverThreshold;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("related-communities-out", 0, &relatedOut),  // (new) after the last perplexity line: `# N K threshold by top min_overlap`, then `k size n l0 o0 l1 o1 ...` per community: its n closest other communities and the nodes it shares with each
-      Option{"related-communities-threshold", 0, "0.05 (new, with --related-communities-out: a node is a member of k iff pi[a, k] >= it)",
-             [&](const std::string& v) {
-               haveRelatedThreshold = true;
-               std::istringstream in(v);
-               in >> relatedThreshold;
-               return !in.fail() && in.eof();
-             }},
-      Option{"related-communities-top", 0, "4 (new, with --related-communities-out: closest communities kept per community, 1..64)",
-             [&](const std::string& v) {
-               haveRelatedTop = true;
-               std::istringstream in(v);
-               in >> relatedTop;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("related-communities-by", 0, &relatedBy),  // (new, with --related-communities-out) jaccard (default) | overlap | contained
-      OptStr("linked-communities-out", 0, &linkedOut),  // (new) after the last perplexity line: `# N K E threshold by top min_links skipped`, then `k size internal n l0 w0 o0 l1 w1 o1 ...` per community: the n other communities it is linked to most, the training links to each and the nodes shared with each
-      Option{"linked-communities-threshold", 0, "0.05 (new, with --linked-communities-out: a node is a member of k iff pi[a, k] >= it)",
-             [&](const std::string& v) {
-               haveLinkedThreshold = true;
-               std::istringstream in(v);
-               in >> linkedThreshold;
-               return !in.fail() && in.eof();
-             }},
-      Option{"linked-communities-top", 0, "4 (new, with --linked-communities-out: partners kept per community, 1..64)",
-             [&](const std::string& v) {
-               haveLinkedTop = true;
-               std::istringstream in(v);
-               in >> linkedTop;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("linked-communities-by", 0, &linkedBy),  // (new, with --linked-communities-out) density (default) | links
-      Option{"linked-communities-min-links", 0, "1 (new, with --linked-communities-out: fewest links that make a partner)",
-             [&](const std::string& v) {
-               haveLinkedMinLinks = true;
-               std::istringstream in(v);
-               in >> linkedMinLinks;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("modularity-out", 0, &modularityOut),  // (new) after the last perplexity line: `# N K E threshold skipped q`, then `k q_k in_k s_k internal volume` per community: the overlapping modularity of the cover against the training links, the 128-bit sums as 32 hexadecimal digits
-      Option{"modularity-threshold", 0, "0.05 (new, with --modularity-out: a node is a member of k iff pi[a, k] >= it)",
-             [&](const std::string& v) {
-               haveModularityThreshold = true;
-               std::istringstream in(v);
-               in >> modularityThreshold;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("node-roles-out", 0, &rolesOut),  // (new) after the last perplexity line: `# N K M threshold among top min_count skipped`, `c k members ksum ksq` per community, `n a degree own embedded reached votes squares nslots k0 c0 f0 ...` per node: how each node sits in the cover against the training adjacency
-      Option{"node-roles-threshold", 0, "0.05 (new, with --node-roles-out: a node is a member of k iff pi[a, k] >= it)",
-             [&](const std::string& v) {
-               haveRolesThreshold = true;
-               std::istringstream in(v);
-               in >> rolesThreshold;
-               return !in.fail() && in.eof();
-             }},
-      Option{"node-roles-top", 0, "4 (new, with --node-roles-out: communities kept per node, 1..16)",
-             [&](const std::string& v) {
-               haveRolesTop = true;
-               std::istringstream in(v);
-               in >> rolesTop;
-               return !in.fail() && in.eof();
-             }},
-      Option{"node-roles-among", 0, "all (new, with --node-roles-out: all = every community a neighbour is in, own = the node's own)",
-             [&](const std::string& v) {
-               haveRolesAmong = true;
-               rolesAmong = v;
-               return true;
-             }},
-      OptStr("triangles-out", 0, &trianglesOut),  // (new) after the last perplexity line: `# N K M threshold skipped dropped total`, `c k members part tri3 wedges` per community, `n a degree tri tri_in tri_comms` per node: the triangles of the training adjacency inside the detected communities
-      Option{"triangles-threshold", 0, "0.05 (new, with --triangles-out: a node is a member of k iff pi[a, k] >= it)",
-             [&](const std::string& v) {
-               haveTrianglesThreshold = true;
-               std::istringstream in(v);
-               in >> trianglesThreshold;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("links-out", 0, &linksOut),      // (new) after the last perplexity line: `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
-      Option{"links-top", 0, "10 (new, with --links-out: most probable partners kept per node, 1..64)",
-             [&](const std::string& v) {
-               haveLinksTop = true;
-               std::istringstream in(v);
-               in >> linksTop;
-               return !in.fail() && in.eof();
-             }},
-      OptStr("links-nodes", 0, &linksNodes),      // (new, with --links-out) file of query node ids; default: every node
-      OptStr("links-exclude", 0, &linksExclude),  // (new, with --links-out) none | training | all (default: training and held-out edges)
-      Option{"membership-top", 0, "4 (new, with --communities-out: strongest communities kept per node, 1..16)",
-             [&](const std::string& v) {
-               haveMembershipTop = true;
-               std::istringstream in(v);
-               in >> membershipTop;
-               return !in.fail() && in.eof();
-             }},
-      Option{"membership-threshold", 0, "0 (new, with --communities-out: a node is a member where pi >= this)",
-             [&](const std::string& v) {
-               haveMembershipThreshold = true;
-               std::istringstream in(v);
-               in >> membershipThreshold;
-               return !in.fail() && in.eof();
-             }},
   };
+
+  // The post-fit outputs (all new): each one's modifiers, then its entry in the table below.
+  Top membershipTop("membership-top", 4, 16, "4 (new, with --communities-out: strongest communities kept per node, 1..16)");
+  Threshold membershipThreshold("membership-threshold", 0, "0 (new, with --communities-out: a node is a member where pi >= this)", false);
+  Top linksTop("links-top", 10, 64, "10 (new, with --links-out: most probable partners kept per node, 1..64)");
+  Text linksNodes("links-nodes");  // file of query node ids; default: every node
+  Choice linksExclude("links-exclude", {"none", "training", "all"}, "all");  // all = training and held-out edges
+  Top linkCommTop("link-communities-top", 1, 16, "1 (new, with --link-communities-out: largest terms kept per link, 1..16)");
+  Threshold linkCommMinTerm("link-communities-min-term", 0, "0 (new, with --link-communities-out: terms below it take no slot)");
+  Threshold qualityThreshold("community-quality-threshold", 0.05, "0.05 (new, with --community-quality-out: a node is a member of k iff pi[a, k] >= it)");
+  // the three cover outputs share this threshold; its rules are written out below
+  Threshold coverThreshold("cover-match-threshold", 0.05, "0.05 (new, with --ground-truth and --cover-match-out: a node is a member of k iff pi[a, k] >= it)");
+  Choice coverOmegaUniverse("cover-omega-universe", {"covered", "all"}, "covered");  // covered = the nodes some ground-truth community holds
+  Threshold relatedThreshold("related-communities-threshold", 0.05, "0.05 (new, with --related-communities-out: a node is a member of k iff pi[a, k] >= it)");
+  Top relatedTop("related-communities-top", 4, 64, "4 (new, with --related-communities-out: closest communities kept per community, 1..64)");
+  Choice relatedBy("related-communities-by", {"jaccard", "overlap", "contained"}, "jaccard");
+  Threshold linkedThreshold("linked-communities-threshold", 0.05, "0.05 (new, with --linked-communities-out: a node is a member of k iff pi[a, k] >= it)");
+  Top linkedTop("linked-communities-top", 4, 64, "4 (new, with --linked-communities-out: partners kept per community, 1..64)");
+  Choice linkedBy("linked-communities-by", {"density", "links"}, "density");
+  Count linkedMinLinks("linked-communities-min-links", 1, "1 (new, with --linked-communities-out: fewest links that make a partner)");
+  Threshold modularityThreshold("modularity-threshold", 0.05, "0.05 (new, with --modularity-out: a node is a member of k iff pi[a, k] >= it)");
+  Threshold rolesThreshold("node-roles-threshold", 0.05, "0.05 (new, with --node-roles-out: a node is a member of k iff pi[a, k] >= it)");
+  Top rolesTop("node-roles-top", 4, 16, "4 (new, with --node-roles-out: communities kept per node, 1..16)");
+  Choice rolesAmong("node-roles-among", {"all", "own"}, "all", "all (new, with --node-roles-out: all = every community a neighbour is in, own = the node's own)");
+  Threshold trianglesThreshold("triangles-threshold", 0.05, "0.05 (new, with --triangles-out: a node is a member of k iff pi[a, k] >= it)");
+
+  using mcmc::Float;
+  using mcmc::Learner;
+  std::vector<uint64_t> truthOffsets;  // --ground-truth, a SNAP cmty file: one community per line; the graph file's own
+  std::vector<uint32_t> truthMembers;  // ids with --file, dense ids with --load-data
+  std::vector<mcmc::Vertex> linkNodes;
+  // In the order the files are written.  Every rank holds all of pi and the training graph, so each analysis is local and
+  // rank 0's file is the answer.  Each file starts with a `#` line, quoted here with the lines that follow it.
+  Output outputs[] = {
+      // `# N K top threshold`, then `k size n0 n1 ...` per community
+      {"communities-out", "communities", {&membershipTop, &membershipThreshold},
+       [&](Learner& l, std::ostream* out) {
+         return l.WriteCommunities(out, static_cast<uint32_t>(membershipTop.value), static_cast<Float>(membershipThreshold.value));
+       }},
+      // `# N K top exclude`, then `a n b0 s0 b1 s1 ...` per query node
+      {"links-out", "links", {&linksTop, &linksNodes, &linksExclude},
+       [&](Learner& l, std::ostream* out) {
+         if (!linksNodes.given) {
+           linkNodes.resize(cfg.N);
+           for (uint64_t v = 0; v < cfg.N; ++v) linkNodes[v] = static_cast<mcmc::Vertex>(v);
+         }
+         const std::string& exclude = linksExclude.Get();
+         const uint32_t mask = exclude == "none" ? 0 : exclude == "training" ? Learner::kExcludeTraining
+                                                                             : Learner::kExcludeTraining | Learner::kExcludeHeldout;
+         return l.WritePredictedLinks(out, linkNodes, static_cast<uint32_t>(linksTop.value), mask);
+       }},
+      // `# N K E top min_term`, then `a b p n k0 t0 k1 t1 ...` per training link
+      {"link-communities-out", "link communities", {&linkCommTop, &linkCommMinTerm},
+       [&](Learner& l, std::ostream* out) {
+         return l.WriteLinkCommunities(out, static_cast<uint32_t>(linkCommTop.value), static_cast<Float>(linkCommMinTerm.value));
+       }},
+      // `# N K E threshold uncovered`, then `k size internal boundary conductance density` per community
+      {"community-quality-out", "community quality", {&qualityThreshold},
+       [&](Learner& l, std::ostream* out) { return l.WriteCommunityQuality(out, static_cast<Float>(qualityThreshold.value)); }},
+      // (with --ground-truth) `# N K G threshold skipped f1_truth f1_detected avg_f1`, then `t g size best overlap f1` per
+      // ground-truth and `d k size best overlap f1` per detected community
+      {"cover-match-out", "cover match", {},
+       [&](Learner& l, std::ostream* out) {
+         return l.WriteCoverMatch(out, truthOffsets, truthMembers, static_cast<Float>(coverThreshold.value));
+       }},
+      // (with --ground-truth) `# N K G threshold skipped nmi_lfk nmi_max`, then `t g size H h` per ground-truth and
+      // `d k size H h` per detected community (H the entropy, h the conditional entropy given the other cover; %.17g)
+      {"cover-nmi-out", "cover NMI", {},
+       [&](Learner& l, std::ostream* out) {
+         return l.WriteCoverNMI(out, truthOffsets, truthMembers, static_cast<Float>(coverThreshold.value));
+       }},
+      // (with --ground-truth) `# N K G threshold universe_n skipped outside omega omega_unadjusted`, then
+      // `j agree detected truth` per level: the pairs of the universe that share j communities (%.17g, `nan` where undefined)
+      {"cover-omega-out", "cover Omega", {&coverOmegaUniverse},
+       [&](Learner& l, std::ostream* out) {
+         const std::vector<uint32_t> universe = Learner::OmegaUniverse(coverOmegaUniverse.Get(), truthMembers, cfg.N);
+         return l.WriteCoverOmega(out, truthOffsets, truthMembers, static_cast<Float>(coverThreshold.value), universe);
+       }},
+      // `# N K threshold by top min_overlap`, then `k size n l0 o0 l1 o1 ...` per community: its n closest other
+      // communities and the nodes it shares with each
+      {"related-communities-out", "related communities", {&relatedThreshold, &relatedTop, &relatedBy},
+       [&](Learner& l, std::ostream* out) {
+         return l.WriteRelatedCommunities(out, static_cast<Float>(relatedThreshold.value), static_cast<uint32_t>(relatedTop.value),
+                                          relatedBy.Get());
+       }},
+      // `# N K E threshold by top min_links skipped`, then `k size internal n l0 w0 o0 l1 w1 o1 ...` per community: the n
+      // other communities it is linked to most, the training links to each and the nodes shared with each
+      {"linked-communities-out", "linked communities", {&linkedThreshold, &linkedTop, &linkedBy, &linkedMinLinks},
+       [&](Learner& l, std::ostream* out) {
+         return l.WriteLinkedCommunities(out, static_cast<Float>(linkedThreshold.value), static_cast<uint32_t>(linkedTop.value),
+                                         linkedBy.Get(), static_cast<uint64_t>(linkedMinLinks.value));
+       }},
+      // `# N K E threshold skipped q`, then `k q_k in_k s_k internal volume` per community: the overlapping modularity of
+      // the cover against the training links, the 128-bit sums as 32 hexadecimal digits
+      {"modularity-out", "modularity", {&modularityThreshold},
+       [&](Learner& l, std::ostream* out) { return l.WriteModularity(out, static_cast<Float>(modularityThreshold.value)); }},
+      // `# N K M threshold among top min_count skipped`, `c k members ksum ksq` per community,
+      // `n a degree own embedded reached votes squares nslots k0 c0 f0 ...` per node: how each node sits in the cover
+      // against the training adjacency
+      {"node-roles-out", "node roles", {&rolesThreshold, &rolesTop, &rolesAmong},
+       [&](Learner& l, std::ostream* out) {
+         return l.WriteNodeRoles(out, static_cast<Float>(rolesThreshold.value), static_cast<uint32_t>(rolesTop.value), rolesAmong.Get());
+       }},
+      // `# N K M threshold skipped dropped total`, `c k members part tri3 wedges` per community,
+      // `n a degree tri tri_in tri_comms` per node: the triangles of the training adjacency inside the detected communities
+      {"triangles-out", "triangles", {&trianglesThreshold},
+       [&](Learner& l, std::ostream* out) { return l.WriteTriangles(out, static_cast<Float>(trianglesThreshold.value)); }},
+  };
+  auto output = [&](const std::string& flag) -> Output& {
+    for (Output& o : outputs)
+      if (o.flag == flag) return o;
+    Fatal("the table of outputs has no --" + flag);
+  };
+  Output &communities = output("communities-out"), &links = output("links-out"), &coverMatch = output("cover-match-out"),
+         &coverNmi = output("cover-nmi-out"), &coverOmega = output("cover-omega-out");
+  // --help lists each output's flag and then its modifiers, in the table's order but for the two oldest: --links-out
+  // comes after the rest, and --communities-out's modifiers last of all
+  auto flag = [&](Output& o) { options.push_back(OptStr(o.flag, 0, &o.file)); };
+  auto modifiers = [&](Output& o) {
+    for (Modifier* m : o.modifiers) options.push_back(m->AsOption());
+  };
+  flag(communities);
+  for (Output& o : outputs) {
+    if (&o == &communities || &o == &links) continue;
+    if (&o == &coverMatch) options.push_back(OptStr("ground-truth", 0, &groundTruth));
+    flag(o);
+    modifiers(o);
+    if (&o == &coverOmega) options.push_back(coverThreshold.AsOption());
+  }
+  flag(links);
+  modifiers(links);
+  modifiers(communities);
   for (int i = 1; i < argc; ++i) {
     std::string arg = argv[i], value;
     if (arg == "--help" || arg == "-h") {
@@ -351,74 +419,35 @@ int main(int argc, char** argv) {
           "sizes before the device has drawn it (use --async 1 without --graph, or the synchronous loop)");
   if (cfg.sampling_stream == "reference" && !cfg.device_sampling)
     Fatal("--sampling-stream reference needs --device-sampling 1 (without it the host samplers draw that same stream)");
-  if ((haveMembershipTop || haveMembershipThreshold) && communitiesOut.empty())
-    Fatal("--membership-top / --membership-threshold need --communities-out FILE");
-  if (membershipTop < 1 || membershipTop > 16) Fatal("--membership-top must be in 1..16");
-  if (!(membershipThreshold >= 0)) Fatal("--membership-threshold must be >= 0");
-  if ((haveLinkCommTop || haveLinkCommMinTerm) && linkCommOut.empty())
-    Fatal("--link-communities-top / --link-communities-min-term need --link-communities-out FILE");
-  if (linkCommTop < 1 || linkCommTop > 16) Fatal("--link-communities-top must be in 1..16");
-  if (!(linkCommMinTerm >= 0) || !std::isfinite(static_cast<float>(linkCommMinTerm)))
-    Fatal("--link-communities-min-term must be finite and >= 0");
-  if (haveQualityThreshold && qualityOut.empty()) Fatal("--community-quality-threshold needs --community-quality-out FILE");
-  if (!(qualityThreshold >= 0) || !std::isfinite(static_cast<float>(qualityThreshold)))
-    Fatal("--community-quality-threshold must be finite and >= 0");
-  if (groundTruth.empty() && !coverMatchOut.empty()) Fatal("--ground-truth FILE and --cover-match-out FILE need each other");
-  if (groundTruth.empty() && !coverNmiOut.empty()) Fatal("--cover-nmi-out FILE needs --ground-truth FILE");
-  if (groundTruth.empty() && !coverOmegaOut.empty()) Fatal("--cover-omega-out FILE needs --ground-truth FILE");
-  if (!groundTruth.empty() && coverMatchOut.empty() && coverNmiOut.empty() && coverOmegaOut.empty())
+  for (const Output& o : outputs) {
+    std::string names;
+    bool given = false;
+    for (const Modifier* m : o.modifiers) {
+      names += (names.empty() ? "--" : " / --") + m->name;
+      given = given || m->given;
+    }
+    if (given && o.file.empty()) Fatal(names + (o.modifiers.size() == 1 ? " needs --" : " need --") + o.flag + " FILE");
+    for (const Modifier* m : o.modifiers) m->Check();
+  }
+  // the cover outputs need --ground-truth, it needs one of them, and so does the threshold they share
+  const bool noCoverOut = coverMatch.file.empty() && coverNmi.file.empty() && coverOmega.file.empty();
+  if (groundTruth.empty() && !coverMatch.file.empty()) Fatal("--ground-truth FILE and --cover-match-out FILE need each other");
+  if (groundTruth.empty() && !coverNmi.file.empty()) Fatal("--cover-nmi-out FILE needs --ground-truth FILE");
+  if (groundTruth.empty() && !coverOmega.file.empty()) Fatal("--cover-omega-out FILE needs --ground-truth FILE");
+  if (!groundTruth.empty() && noCoverOut)
     Fatal("--ground-truth FILE and --cover-match-out FILE need each other (or --cover-nmi-out FILE, or --cover-omega-out FILE)");
-  if (haveCoverThreshold && coverMatchOut.empty() && coverNmiOut.empty() && coverOmegaOut.empty())
+  if (coverThreshold.given && noCoverOut)
     Fatal("--cover-match-threshold needs --ground-truth FILE and --cover-match-out FILE (or --cover-nmi-out FILE, or --cover-omega-out FILE)");
-  if (!coverOmegaUniverse.empty() && coverOmegaOut.empty()) Fatal("--cover-omega-universe needs --cover-omega-out FILE");
-  if (!coverOmegaUniverse.empty() && coverOmegaUniverse != "covered" && coverOmegaUniverse != "all")
-    Fatal("--cover-omega-universe must be covered or all");
-  if (!(coverThreshold >= 0) || !std::isfinite(static_cast<float>(coverThreshold)))
-    Fatal("--cover-match-threshold must be finite and >= 0");
-  if ((haveRelatedThreshold || haveRelatedTop || !relatedBy.empty()) && relatedOut.empty())
-    Fatal("--related-communities-threshold / --related-communities-top / --related-communities-by need --related-communities-out FILE");
-  if (!relatedBy.empty() && relatedBy != "jaccard" && relatedBy != "overlap" && relatedBy != "contained")
-    Fatal("--related-communities-by must be jaccard, overlap or contained");
-  if (relatedTop < 1 || relatedTop > 64) Fatal("--related-communities-top must be in 1..64");
-  if (!(relatedThreshold >= 0) || !std::isfinite(static_cast<float>(relatedThreshold)))
-    Fatal("--related-communities-threshold must be finite and >= 0");
-  if ((haveLinkedThreshold || haveLinkedTop || haveLinkedMinLinks || !linkedBy.empty()) && linkedOut.empty())
-    Fatal("--linked-communities-threshold / --linked-communities-top / --linked-communities-by / --linked-communities-min-links need --linked-communities-out FILE");
-  if (!linkedBy.empty() && linkedBy != "density" && linkedBy != "links")
-    Fatal("--linked-communities-by must be density or links");
-  if (linkedTop < 1 || linkedTop > 64) Fatal("--linked-communities-top must be in 1..64");
-  if (!(linkedThreshold >= 0) || !std::isfinite(static_cast<float>(linkedThreshold)))
-    Fatal("--linked-communities-threshold must be finite and >= 0");
-  if (linkedMinLinks < 0) Fatal("--linked-communities-min-links must be >= 0");
-  if (haveModularityThreshold && modularityOut.empty()) Fatal("--modularity-threshold needs --modularity-out FILE");
-  if (!(modularityThreshold >= 0) || !std::isfinite(static_cast<float>(modularityThreshold)))
-    Fatal("--modularity-threshold must be finite and >= 0");
-  if ((haveRolesThreshold || haveRolesTop || haveRolesAmong) && rolesOut.empty())
-    Fatal("--node-roles-threshold / --node-roles-top / --node-roles-among need --node-roles-out FILE");
-  if (!(rolesThreshold >= 0) || !std::isfinite(static_cast<float>(rolesThreshold)))
-    Fatal("--node-roles-threshold must be finite and >= 0");
-  if (rolesTop < 1 || rolesTop > 16) Fatal("--node-roles-top must be in 1..16");
-  if (rolesAmong != "all" && rolesAmong != "own") Fatal("--node-roles-among must be all or own");
-  if (haveTrianglesThreshold && trianglesOut.empty()) Fatal("--triangles-threshold needs --triangles-out FILE");
-  if (!(trianglesThreshold >= 0) || !std::isfinite(static_cast<float>(trianglesThreshold)))
-    Fatal("--triangles-threshold must be finite and >= 0");
-  if ((haveLinksTop || !linksNodes.empty() || !linksExclude.empty()) && linksOut.empty())
-    Fatal("--links-top / --links-nodes / --links-exclude need --links-out FILE");
-  if (linksTop < 1 || linksTop > 64) Fatal("--links-top must be in 1..64");
-  uint32_t linksMask = mcmc::Learner::kExcludeTraining | mcmc::Learner::kExcludeHeldout;
-  if (linksExclude == "none") linksMask = 0;
-  else if (linksExclude == "training") linksMask = mcmc::Learner::kExcludeTraining;
-  else if (!linksExclude.empty() && linksExclude != "all") Fatal("--links-exclude must be none, training or all");
-  std::vector<mcmc::Vertex> linkNodes;
-  if (!linksNodes.empty()) {
-    std::ifstream in(linksNodes);
-    if (!in.good()) Fatal("cannot read --links-nodes file " + linksNodes);
+  coverThreshold.Check();
+  if (linksNodes.given) {
+    std::ifstream in(linksNodes.value);
+    if (!in.good()) Fatal("cannot read --links-nodes file " + linksNodes.value);
     unsigned long long v;
     while (in >> v) {
       if (v > 0xFFFFFFFFull) Fatal("--links-nodes: node id " + std::to_string(v) + " is not a node id");
       linkNodes.push_back(static_cast<mcmc::Vertex>(v));
     }
-    if (!in.eof()) Fatal("--links-nodes: " + linksNodes + " holds something that is not a node id");
+    if (!in.eof()) Fatal("--links-nodes: " + linksNodes.value + " holds something that is not a node id");
   }
   if (!loadDataset && !FileExists(filename)) Fatal("Failed to detect file: " + filename);  // main.cc:91-96
   if (loadDataset && loadFile.empty()) Fatal("load-file is required with load-data");
@@ -438,8 +467,6 @@ int main(int argc, char** argv) {
   if (!mcmc::GenerateSetsFromEdges(cfg.N, unique_edges, cfg.heldout_ratio, &cfg.training_edges, &cfg.heldout_edges,
                                    &cfg.training, &cfg.heldout))
     Fatal("Failed to generate training/heldout sets");
-  std::vector<uint64_t> truthOffsets;
-  std::vector<uint32_t> truthMembers;
   if (!groundTruth.empty()) {
     // a text graph's ground truth speaks of the graph file's own ids, a data-set dump's of dense ids
     uint64_t dropped = 0;
@@ -508,163 +535,15 @@ int main(int argc, char** argv) {
     std::ofstream out(rank == 0 ? ckptOut : std::string("/dev/null"), std::ios::binary);
     if (!learner.Serialize(&out)) Fatal("cannot write checkpoint " + ckptOut);
   }
-  if (!communitiesOut.empty()) {
-    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
+  for (Output& o : outputs) {
+    if (o.file.empty()) continue;
     try {
       if (rank == 0) {
-        std::ofstream out(communitiesOut);
-        if (!out.good() || !learner.WriteCommunities(&out, static_cast<uint32_t>(membershipTop),
-                                                     static_cast<mcmc::Float>(membershipThreshold)))
-          Fatal("cannot write communities " + communitiesOut);
+        std::ofstream out(o.file);
+        if (!out.good() || !o.write(learner, &out)) Fatal("cannot write " + o.words + " " + o.file);
       }
     } catch (const std::exception& e) {
-      Fatal(std::string("communities: ") + e.what());
-    }
-  }
-  if (!linksOut.empty()) {
-    // every rank holds all of pi: link prediction is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        if (linksNodes.empty()) {
-          linkNodes.resize(cfg.N);
-          for (uint64_t v = 0; v < cfg.N; ++v) linkNodes[v] = static_cast<mcmc::Vertex>(v);
-        }
-        std::ofstream out(linksOut);
-        if (!out.good() || !learner.WritePredictedLinks(&out, linkNodes, static_cast<uint32_t>(linksTop), linksMask))
-          Fatal("cannot write links " + linksOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("links: ") + e.what());
-    }
-  }
-  if (!linkCommOut.empty()) {
-    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(linkCommOut);
-        if (!out.good() || !learner.WriteLinkCommunities(&out, static_cast<uint32_t>(linkCommTop),
-                                                         static_cast<mcmc::Float>(linkCommMinTerm)))
-          Fatal("cannot write link communities " + linkCommOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("link communities: ") + e.what());
-    }
-  }
-  if (!qualityOut.empty()) {
-    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(qualityOut);
-        if (!out.good() || !learner.WriteCommunityQuality(&out, static_cast<mcmc::Float>(qualityThreshold)))
-          Fatal("cannot write community quality " + qualityOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("community quality: ") + e.what());
-    }
-  }
-  if (!coverMatchOut.empty()) {
-    // every rank holds all of pi: the comparison is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(coverMatchOut);
-        if (!out.good() || !learner.WriteCoverMatch(&out, truthOffsets, truthMembers, static_cast<mcmc::Float>(coverThreshold)))
-          Fatal("cannot write cover match " + coverMatchOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("cover match: ") + e.what());
-    }
-  }
-  if (!coverNmiOut.empty()) {
-    // every rank holds all of pi: the comparison is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(coverNmiOut);
-        if (!out.good() || !learner.WriteCoverNMI(&out, truthOffsets, truthMembers, static_cast<mcmc::Float>(coverThreshold)))
-          Fatal("cannot write cover NMI " + coverNmiOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("cover NMI: ") + e.what());
-    }
-  }
-  if (!coverOmegaOut.empty()) {
-    // every rank holds all of pi: the comparison is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        const std::vector<uint32_t> universe = mcmc::Learner::OmegaUniverse(
-            coverOmegaUniverse.empty() ? "covered" : coverOmegaUniverse, truthMembers, cfg.N);
-        std::ofstream out(coverOmegaOut);
-        if (!out.good() ||
-            !learner.WriteCoverOmega(&out, truthOffsets, truthMembers, static_cast<mcmc::Float>(coverThreshold), universe))
-          Fatal("cannot write cover Omega " + coverOmegaOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("cover Omega: ") + e.what());
-    }
-  }
-  if (!relatedOut.empty()) {
-    // every rank holds all of pi: the read-out is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(relatedOut);
-        if (!out.good() || !learner.WriteRelatedCommunities(&out, static_cast<mcmc::Float>(relatedThreshold),
-                                                            static_cast<uint32_t>(relatedTop),
-                                                            relatedBy.empty() ? "jaccard" : relatedBy))
-          Fatal("cannot write related communities " + relatedOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("related communities: ") + e.what());
-    }
-  }
-  if (!linkedOut.empty()) {
-    // every rank holds all of pi and the training links: the read-out is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(linkedOut);
-        if (!out.good() || !learner.WriteLinkedCommunities(&out, static_cast<mcmc::Float>(linkedThreshold),
-                                                           static_cast<uint32_t>(linkedTop),
-                                                           linkedBy.empty() ? "density" : linkedBy,
-                                                           static_cast<uint64_t>(linkedMinLinks)))
-          Fatal("cannot write linked communities " + linkedOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("linked communities: ") + e.what());
-    }
-  }
-  if (!modularityOut.empty()) {
-    // every rank holds all of pi and the training links: the read-out is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(modularityOut);
-        if (!out.good() || !learner.WriteModularity(&out, static_cast<mcmc::Float>(modularityThreshold)))
-          Fatal("cannot write modularity " + modularityOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("modularity: ") + e.what());
-    }
-  }
-  if (!rolesOut.empty()) {
-    // every rank holds all of pi and the training adjacency: the read-out is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(rolesOut);
-        if (!out.good() || !learner.WriteNodeRoles(&out, static_cast<mcmc::Float>(rolesThreshold),
-                                                   static_cast<uint32_t>(rolesTop), rolesAmong))
-          Fatal("cannot write node roles " + rolesOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("node roles: ") + e.what());
-    }
-  }
-  if (!trianglesOut.empty()) {
-    // every rank holds all of pi and the training links: the read-out is local, rank 0's file is the answer
-    try {
-      if (rank == 0) {
-        std::ofstream out(trianglesOut);
-        if (!out.good() || !learner.WriteTriangles(&out, static_cast<mcmc::Float>(trianglesThreshold)))
-          Fatal("cannot write triangles " + trianglesOut);
-      }
-    } catch (const std::exception& e) {
-      Fatal(std::string("triangles: ") + e.what());
+      Fatal(o.words + ": " + e.what());
     }
   }
   learner.PrintStats();

@@ -57,6 +57,179 @@ def test_error_exits(exe, tmp_path):
     assert r.returncode != 0 and "invalid" in r.stderr
 
 
+def test_help_is_the_recorded_text(exe):
+    """tests/golden/ammsb_main_help.txt is the stdout of `ammsb_main --help` as built from the commit before the driver's
+    post-fit flags came from one table: every flag, default and help text, in that order, byte for byte."""
+    out = subprocess.run([exe, "--help"], capture_output=True, timeout=60)
+    with open(os.path.join(ROOT, "tests", "golden", "ammsb_main_help.txt"), "rb") as f:
+        assert out.stdout == f.read()
+    assert out.returncode == 1
+
+
+# The post-fit flag rules: (the flags that break one rule and no other, the driver's `F` line), the texts as the driver
+# had them when each rule was written out by hand.  OUT stands for a file that must not appear, NODES for a readable
+# file of node ids; the ground-truth file is only read after the graph, so it need not exist.
+OUT, NODES = "@out", "@nodes"
+FINITE = " must be finite and >= 0"
+NEED_MEMBERSHIP = "--membership-top / --membership-threshold need --communities-out FILE"
+NEED_LINKCOMM = "--link-communities-top / --link-communities-min-term need --link-communities-out FILE"
+NEED_RELATED = "--related-communities-threshold / --related-communities-top / --related-communities-by need --related-communities-out FILE"
+NEED_LINKED = ("--linked-communities-threshold / --linked-communities-top / --linked-communities-by / --linked-communities-min-links "
+               "need --linked-communities-out FILE")
+NEED_ROLES = "--node-roles-threshold / --node-roles-top / --node-roles-among need --node-roles-out FILE"
+NEED_LINKS = "--links-top / --links-nodes / --links-exclude need --links-out FILE"
+NEED_COVER_OUT = "--ground-truth FILE and --cover-match-out FILE need each other (or --cover-nmi-out FILE, or --cover-omega-out FILE)"
+GT = ["--ground-truth", "truth.txt"]
+ONE_RULE = [
+    (["--membership-top", "4"], NEED_MEMBERSHIP),
+    (["--membership-threshold", "0.1"], NEED_MEMBERSHIP),
+    (["--communities-out", OUT, "--membership-top", "0"], "--membership-top must be in 1..16"),
+    (["--communities-out", OUT, "--membership-top", "17"], "--membership-top must be in 1..16"),
+    (["--communities-out", OUT, "--membership-threshold", "-0.1"], "--membership-threshold must be >= 0"),
+    (["--link-communities-top", "1"], NEED_LINKCOMM),
+    (["--link-communities-min-term", "0"], NEED_LINKCOMM),
+    (["--link-communities-out", OUT, "--link-communities-top", "0"], "--link-communities-top must be in 1..16"),
+    (["--link-communities-out", OUT, "--link-communities-top", "17"], "--link-communities-top must be in 1..16"),
+    (["--link-communities-out", OUT, "--link-communities-min-term", "-1e-9"], "--link-communities-min-term" + FINITE),
+    (["--link-communities-out", OUT, "--link-communities-min-term", "1e39"], "--link-communities-min-term" + FINITE),
+    (["--community-quality-threshold", "0.05"], "--community-quality-threshold needs --community-quality-out FILE"),
+    (["--community-quality-out", OUT, "--community-quality-threshold", "-0.1"], "--community-quality-threshold" + FINITE),
+    (["--community-quality-out", OUT, "--community-quality-threshold", "1e39"], "--community-quality-threshold" + FINITE),
+    (["--cover-match-out", OUT], "--ground-truth FILE and --cover-match-out FILE need each other"),
+    (["--cover-nmi-out", OUT], "--cover-nmi-out FILE needs --ground-truth FILE"),
+    (["--cover-omega-out", OUT], "--cover-omega-out FILE needs --ground-truth FILE"),
+    (GT, NEED_COVER_OUT),
+    (GT + ["--modularity-out", OUT], NEED_COVER_OUT),
+    (["--cover-match-threshold", "0.1"],
+     "--cover-match-threshold needs --ground-truth FILE and --cover-match-out FILE (or --cover-nmi-out FILE, or --cover-omega-out FILE)"),
+    (["--cover-omega-universe", "all"], "--cover-omega-universe needs --cover-omega-out FILE"),
+    (GT + ["--cover-match-out", OUT, "--cover-omega-universe", "all"], "--cover-omega-universe needs --cover-omega-out FILE"),
+    (GT + ["--cover-omega-out", OUT, "--cover-omega-universe", "every"], "--cover-omega-universe must be covered or all"),
+    (GT + ["--cover-match-out", OUT, "--cover-match-threshold", "-0.1"], "--cover-match-threshold" + FINITE),
+    (GT + ["--cover-nmi-out", OUT, "--cover-match-threshold", "1e39"], "--cover-match-threshold" + FINITE),
+    (["--related-communities-threshold", "0.1"], NEED_RELATED),
+    (["--related-communities-top", "4"], NEED_RELATED),
+    (["--related-communities-by", "overlap"], NEED_RELATED),
+    (["--related-communities-out", OUT, "--related-communities-by", "cosine"], "--related-communities-by must be jaccard, overlap or contained"),
+    (["--related-communities-out", OUT, "--related-communities-top", "0"], "--related-communities-top must be in 1..64"),
+    (["--related-communities-out", OUT, "--related-communities-top", "65"], "--related-communities-top must be in 1..64"),
+    (["--related-communities-out", OUT, "--related-communities-threshold", "-1"], "--related-communities-threshold" + FINITE),
+    (["--related-communities-out", OUT, "--related-communities-threshold", "1e39"], "--related-communities-threshold" + FINITE),
+    (["--linked-communities-threshold", "0.1"], NEED_LINKED),
+    (["--linked-communities-top", "4"], NEED_LINKED),
+    (["--linked-communities-by", "links"], NEED_LINKED),
+    (["--linked-communities-min-links", "2"], NEED_LINKED),
+    (["--linked-communities-out", OUT, "--linked-communities-by", "weight"], "--linked-communities-by must be density or links"),
+    (["--linked-communities-out", OUT, "--linked-communities-top", "0"], "--linked-communities-top must be in 1..64"),
+    (["--linked-communities-out", OUT, "--linked-communities-top", "65"], "--linked-communities-top must be in 1..64"),
+    (["--linked-communities-out", OUT, "--linked-communities-threshold", "-1"], "--linked-communities-threshold" + FINITE),
+    (["--linked-communities-out", OUT, "--linked-communities-threshold", "1e39"], "--linked-communities-threshold" + FINITE),
+    (["--linked-communities-out", OUT, "--linked-communities-min-links", "-1"], "--linked-communities-min-links must be >= 0"),
+    (["--modularity-threshold", "0.1"], "--modularity-threshold needs --modularity-out FILE"),
+    (["--modularity-out", OUT, "--modularity-threshold", "-1"], "--modularity-threshold" + FINITE),
+    (["--modularity-out", OUT, "--modularity-threshold", "1e39"], "--modularity-threshold" + FINITE),
+    (["--node-roles-threshold", "0.1"], NEED_ROLES),
+    (["--node-roles-top", "4"], NEED_ROLES),
+    (["--node-roles-among", "own"], NEED_ROLES),
+    (["--node-roles-among", ""], NEED_ROLES),
+    (["--node-roles-out", OUT, "--node-roles-threshold", "-1"], "--node-roles-threshold" + FINITE),
+    (["--node-roles-out", OUT, "--node-roles-threshold", "1e39"], "--node-roles-threshold" + FINITE),
+    (["--node-roles-out", OUT, "--node-roles-top", "0"], "--node-roles-top must be in 1..16"),
+    (["--node-roles-out", OUT, "--node-roles-top", "17"], "--node-roles-top must be in 1..16"),
+    (["--node-roles-out", OUT, "--node-roles-among", "some"], "--node-roles-among must be all or own"),
+    (["--node-roles-out", OUT, "--node-roles-among", ""], "--node-roles-among must be all or own"),
+    (["--triangles-threshold", "0.1"], "--triangles-threshold needs --triangles-out FILE"),
+    (["--triangles-out", OUT, "--triangles-threshold", "-1"], "--triangles-threshold" + FINITE),
+    (["--triangles-out", OUT, "--triangles-threshold", "1e39"], "--triangles-threshold" + FINITE),
+    (["--links-top", "10"], NEED_LINKS),
+    (["--links-nodes", NODES], NEED_LINKS),
+    (["--links-exclude", "none"], NEED_LINKS),
+    (["--links-out", OUT, "--links-top", "0"], "--links-top must be in 1..64"),
+    (["--links-out", OUT, "--links-top", "65"], "--links-top must be in 1..64"),
+    (["--links-out", OUT, "--links-exclude", "heldout"], "--links-exclude must be none, training or all"),
+    # each kind of modifier as --name=value
+    (["--triangles-out=" + OUT, "--triangles-threshold=-1"], "--triangles-threshold" + FINITE),
+    (["--node-roles-top=4"], NEED_ROLES),
+    (["--node-roles-out=" + OUT, "--node-roles-top=17"], "--node-roles-top must be in 1..16"),
+    (["--node-roles-out=" + OUT, "--node-roles-among=some"], "--node-roles-among must be all or own"),
+    (["--linked-communities-out=" + OUT, "--linked-communities-min-links=-1"], "--linked-communities-min-links must be >= 0"),
+    (["--links-exclude=none"], NEED_LINKS),
+    # of a repeated flag the last one counts
+    (["--node-roles-out", OUT, "--node-roles-top", "4", "--node-roles-top", "17"], "--node-roles-top must be in 1..16"),
+    (["--links-out", OUT, "--links-exclude", "none", "--links-exclude", "heldout"], "--links-exclude must be none, training or all"),
+    # a value that is not one: every kind reads the whole of its argument
+    (["--modularity-out", OUT, "--modularity-threshold", "half"], "the argument ('half') for option '--modularity-threshold' is invalid"),
+    (["--modularity-out", OUT, "--modularity-threshold", "0.1x"], "the argument ('0.1x') for option '--modularity-threshold' is invalid"),
+    (["--modularity-out", OUT, "--modularity-threshold="], "the argument ('') for option '--modularity-threshold' is invalid"),
+    (["--communities-out", OUT, "--membership-threshold", "0.1x"], "the argument ('0.1x') for option '--membership-threshold' is invalid"),
+    (["--links-out", OUT, "--links-top", "half"], "the argument ('half') for option '--links-top' is invalid"),
+    (["--links-out", OUT, "--links-top", "4x"], "the argument ('4x') for option '--links-top' is invalid"),
+    (["--links-out", OUT, "--links-top", "nan"], "the argument ('nan') for option '--links-top' is invalid"),
+    (["--links-out", OUT, "--links-top=1.5"], "the argument ('1.5') for option '--links-top' is invalid"),
+    (["--linked-communities-out", OUT, "--linked-communities-min-links", "half"],
+     "the argument ('half') for option '--linked-communities-min-links' is invalid"),
+    (["--linked-communities-out", OUT, "--linked-communities-min-links", "2x"],
+     "the argument ('2x') for option '--linked-communities-min-links' is invalid"),
+]
+# two rules broken at once: which of the two messages comes is the table's business
+TWO_RULES = [
+    ["--node-roles-top", "0"],                                                      # needs its -out, and out of range
+    ["--node-roles-out", OUT, "--node-roles-top", "0", "--node-roles-threshold", "-1"],
+    ["--modularity-threshold", "0.1", "--triangles-threshold", "0.1"],
+]
+EVERY_OUT = [f for name in ("communities", "links", "link-communities", "community-quality", "cover-match", "cover-nmi", "cover-omega",
+                            "related-communities", "linked-communities", "modularity", "node-roles", "triangles")
+             for f in ("--%s-out" % name, OUT + "." + name)]
+ACCEPTED = [
+    [],
+    GT + EVERY_OUT,
+    GT + EVERY_OUT + ["--membership-top", "16", "--membership-threshold", "1e39", "--links-top", "64", "--links-nodes", NODES,
+                      "--links-exclude", "training", "--link-communities-top", "16", "--link-communities-min-term", "1e-3",
+                      "--community-quality-threshold", "0", "--cover-match-threshold", "0.5", "--cover-omega-universe", "all",
+                      "--related-communities-threshold", "1", "--related-communities-top", "64", "--related-communities-by", "contained",
+                      "--linked-communities-threshold", "1e38", "--linked-communities-top", "1", "--linked-communities-by", "links",
+                      "--linked-communities-min-links", "0", "--modularity-threshold", "0.25", "--node-roles-threshold", "0.1",
+                      "--node-roles-top", "1", "--node-roles-among", "own", "--triangles-threshold", "1e-30"],
+    GT + ["--cover-nmi-out", OUT, "--cover-match-threshold=0.2"],
+    GT + ["--cover-omega-out=" + OUT, "--cover-omega-universe=covered"],
+    ["--node-roles-out", OUT, "--node-roles-top", "17", "--node-roles-top", "4"],   # the last one counts
+    ["--node-roles-out=" + OUT, "--node-roles-among=all"],
+    # an empty word is the default where --help names none, and then the flag does not count as given
+    ["--related-communities-by", "", "--linked-communities-by=", "--links-exclude", "", "--cover-omega-universe", "", "--links-nodes", ""],
+    ["--related-communities-out", OUT, "--related-communities-by", "overlap", "--related-communities-by", ""],
+]
+
+
+def _postfit_flags(tmp_path, flags):
+    nodes = tmp_path / "nodes.txt"
+    nodes.write_text("0 1\n2\n")
+    r = subprocess.run([EXE, "-f", str(tmp_path / "no-such-graph.txt"), "-k", "8"] +
+                       [f.replace(OUT, str(tmp_path / "out")).replace(NODES, str(nodes)) for f in flags],
+                       capture_output=True, text=True, timeout=60)
+    assert sorted(os.listdir(tmp_path)) == ["nodes.txt"], flags           # no output file, whatever it would be called
+    return r
+
+
+@pytest.mark.parametrize("flags,message", ONE_RULE, ids=lambda v: " ".join(v) if isinstance(v, list) else None)
+def test_one_broken_postfit_rule_ends_with_its_message_before_the_graph_is_read(exe, tmp_path, flags, message):
+    r = _postfit_flags(tmp_path, flags)
+    assert r.returncode == 2 and "Failed to detect file" not in r.stderr, r.stderr[-500:]
+    assert r.stderr.splitlines()[1:] == ["F " + message] and r.stdout == ""   # (the first line repeats the command line)
+
+
+@pytest.mark.parametrize("flags", TWO_RULES, ids=" ".join)
+def test_two_broken_postfit_rules_end_with_status_2_before_the_graph_is_read(exe, tmp_path, flags):
+    r = _postfit_flags(tmp_path, flags)
+    assert r.returncode == 2 and "Failed to detect file" not in r.stderr, r.stderr[-500:]
+    assert r.stderr.splitlines()[-1].startswith("F --"), r.stderr[-500:]
+
+
+@pytest.mark.parametrize("flags", ACCEPTED, ids=lambda v: " ".join(v)[:80] or "none")
+def test_accepted_postfit_flags_get_as_far_as_the_graph_file(exe, tmp_path, flags):
+    r = _postfit_flags(tmp_path, flags)
+    assert r.returncode == 2 and r.stderr.splitlines()[-1].startswith("F Failed to detect file: "), r.stderr[-500:]
+
+
 def _snap_file(path, N=3000, deg=12, seed=4):
     rng = np.random.default_rng(seed)
     comm = rng.integers(0, 8, N)
