@@ -272,6 +272,33 @@ class Learner {
   // tri_comms` per node: integers throughout.
   bool WriteTriangles(std::ostream* out, Float threshold, const std::vector<Edge>* edges = nullptr);
 
+  // Is each community one piece?  The connected components of every community of the cover pi[a, k] >= threshold inside the
+  // graph of `edges` (nullptr: every training link once; else the keys (a << 32) | b, either order of the ends, duplicates
+  // and a == a valid, a key with an end >= N counted in skipped), the integers of include/ammsb_components.h: per community
+  // members, components, largest, largest_root (-1: empty), singletons; the memberships as a CSR over the nodes, offsets
+  // [N + 1] (a host prefix sum over the downloaded own) and per slot community, root (the smallest node of its component),
+  // size; stray per node; links, skipped, shared, all exact.  Derive() is the header's float64 statement over them.
+  // std::invalid_argument on a bad threshold, on a cover of 2^32 memberships or more (the message names the threshold) and
+  // on a list of 2^31 keys or more; std::runtime_error where the library gave a union up.  Waits, reads and perturbs like
+  // CommunityQuality.
+  struct ComponentsResult {
+    std::vector<uint64_t> members, components, singletons;  // [K]
+    std::vector<uint32_t> largest;                           // [K]
+    std::vector<int32_t> largest_root;                       // [K]
+    std::vector<uint64_t> offsets;                           // [N + 1]
+    std::vector<uint16_t> community;                         // [M]
+    std::vector<uint32_t> root, size;                        // [M]
+    std::vector<uint32_t> stray;                             // [N]
+    uint64_t links = 0, skipped = 0, shared = 0;
+    std::vector<double> giant, fragmentation;                // [K], -1 where members is 0
+    double connected = -1;
+    void Derive();
+  };
+  void CommunityComponents(Float threshold, ComponentsResult* result, const std::vector<Edge>* edges = nullptr);
+  // `# N K E M threshold skipped shared`, `c k members components largest largest_root singletons` per community, `n a
+  // nslots k0 root0 size0 ...` per node: integers throughout.
+  bool WriteCommunityComponents(std::ostream* out, Float threshold, const std::vector<Edge>* edges = nullptr);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

@@ -1,8 +1,9 @@
 // mcmc::Learner's post-fit analyses (include/mcmc/learner.h): what reads a fitted model out -- memberships and
 // communities, link prediction, link communities, community quality, the three comparisons with a ground-truth cover
 // (F1 match, overlapping NMI, Omega index), how the detected communities relate to each other, how they are linked, the
-// overlapping modularity of the cover, the role of every node in it and the triangles inside the communities.  Each is
-// a thin driver of one library of its own (libammsb_readout.so ... libammsb_triangles.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
+// overlapping modularity of the cover, the role of every node in it, the triangles inside the communities and the connected
+// components of each.  Each is
+// a thin driver of one library of its own (libammsb_readout.so ... libammsb_components.so): check the arguments, drain the training loop, run the library in slabs of a fixed byte budget,
 // read the results back, and for the Write* methods print them.  Nothing here touches the training loop of learner.cc.
 #include "mcmc/learner.h"
 #include "ammsb_readout.h"
@@ -17,6 +18,7 @@
 #include "ammsb_modularity.h"
 #include "ammsb_roles.h"
 #include "ammsb_triangles.h"
+#include "ammsb_components.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1266,6 +1268,139 @@ bool Learner::WriteTriangles(std::ostream* out, Float threshold, const std::vect
     *out << "c " << k << " " << r.kmembers[k] << " " << r.kpart[k] << " " << r.ktri3[k] << " " << r.wedges[k] << "\n";
   for (size_t a = 0; a < r.degree.size(); ++a)
     *out << "n " << a << " " << r.degree[a] << " " << r.tri[a] << " " << r.tri_in[a] << " " << r.tri_comms[a] << "\n";
+  return static_cast<bool>(*out);
+}
+
+// ---- is each community one piece: libammsb_components.so over libammsb_connect.so's mask of pi and an edge list
+void Learner::ComponentsResult::Derive() {
+#pragma STDC FP_CONTRACT OFF
+  const size_t K = members.size();
+  giant.assign(K, -1.0);
+  fragmentation.assign(K, -1.0);
+  uint64_t some = 0, whole = 0;
+  for (size_t k = 0; k < K; ++k) {
+    whole += components[k] == 1;
+    if (members[k] == 0) continue;
+    ++some;
+    // (every integer is converted once, to nearest even)
+    giant[k] = static_cast<double>(largest[k]) / static_cast<double>(members[k]);
+    fragmentation[k] = 1.0 - giant[k];
+  }
+  connected = some ? static_cast<double>(whole) / static_cast<double>(some) : -1.0;
+}
+
+void Learner::CommunityComponents(Float threshold, ComponentsResult* result, const std::vector<Edge>* edges) {
+  CheckThreshold("CommunityComponents", threshold);
+  if (edges && edges->size() >= AMMSB_COMPONENTS_MAX_EDGES)
+    throw std::invalid_argument("CommunityComponents: an edge list of 2^31 keys or more");
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  if (K == 0 || K > AMMSB_COMPONENTS_MAX_COLS) throw std::runtime_error("CommunityComponents: K outside 1..8192");
+  std::vector<Edge> training;
+  if (!edges) {
+    training = SortedTrainingLinks(cfg_);
+    if (training.size() >= AMMSB_COMPONENTS_MAX_EDGES)
+      throw std::invalid_argument("CommunityComponents: 2^31 training links or more");
+    edges = &training;
+  }
+  ComponentsResult& r = *result;
+  r.members.assign(K, 0);
+  r.components.assign(K, 0);
+  r.singletons.assign(K, 0);
+  r.largest.assign(K, 0);
+  r.largest_root.assign(K, -1);
+  r.offsets.assign(N + 1, 0);
+  r.community.clear();
+  r.root.clear();
+  r.size.clear();
+  r.stray.assign(N, 0);
+  r.links = r.shared = 0;
+  r.skipped = edges->size();  // (without a node every key has an end >= N)
+  if (N > 0) {
+    const uint32_t cols = static_cast<uint32_t>(K);
+    hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
+    const clcuda::Context context = queue_.GetContext();
+    const uint64_t words = ammsb_connect_mask_bytes(N, cols) / sizeof(uint64_t);
+    clcuda::Buffer<uint64_t> d_mask(context, words);
+    clcuda::Buffer<uint32_t> d_node(context, 2 * N);  // own, then stray
+    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
+    rc = ammsb_components_own(d_mask(), N, cols, d_node(), stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_components_own", rc, ammsb_components_last_error());
+    // base: a host prefix sum over the downloaded own
+    std::vector<uint32_t> own(N);
+    d_node.Read(queue_, N, own.data());
+    queue_.Finish();
+    for (uint64_t a = 0; a < N; ++a) r.offsets[a + 1] = r.offsets[a] + own[a];
+    const uint64_t M = r.offsets[N];
+    if (M >= AMMSB_COMPONENTS_MAX_SLOTS)
+      throw std::invalid_argument("CommunityComponents: the cover has " + std::to_string(M) + " memberships at the threshold " +
+                                  G9(threshold) + "; the library takes fewer than 2^32 (raise the threshold)");
+    const uint64_t m1 = std::max<uint64_t>(M, 1);  // (a buffer needs a byte)
+    clcuda::Buffer<uint64_t> d_base(context, queue_, r.offsets.begin(), r.offsets.end());
+    clcuda::Buffer<uint64_t> d_sums(context, 4 * K + 4);  // members components singletons best; counts
+    clcuda::Buffer<uint32_t> d_slot(context, 4 * m1), d_best(context, 2 * K);  // slot_node parent root size; largest largest_root
+    clcuda::Buffer<uint16_t> d_comm(context, m1);
+    const hipError_t e = hipMemsetAsync(d_sums(), 0, (4 * K + 4) * sizeof(uint64_t), stream);
+    if (e != hipSuccess) throw std::runtime_error(std::string("CommunityComponents: memset: ") + hipGetErrorString(e));
+    uint32_t* const parent = d_slot() + m1;
+    uint64_t* const counts = d_sums() + 4 * K;
+    if (M > 0) {
+      rc = ammsb_components_slots(d_mask(), N, cols, d_base(), M, 0, N, d_slot(), d_comm(), parent, stream);
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_components_slots", rc, ammsb_components_last_error());
+    }
+    if (!edges->empty()) {
+      clcuda::Buffer<Edge> d_edges(context, queue_, edges->begin(), edges->end());
+      rc = ammsb_components_edges(d_mask(), N, cols, d_base(), M, d_edges(), edges->size(), parent, counts, stream);
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_components_edges", rc, ammsb_components_last_error());
+      queue_.Finish();  // (the keys' buffer goes out of scope)
+    }
+    rc = ammsb_components_finish(N, cols, d_base(), M, d_slot(), d_comm(), parent, d_slot() + 2 * m1, d_slot() + 3 * m1, d_sums(),
+                                 d_sums() + K, d_sums() + 2 * K, d_sums() + 3 * K, d_best(),
+                                 reinterpret_cast<int32_t*>(d_best() + K), d_node() + N, counts, stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_components_finish", rc, ammsb_components_last_error());
+    std::vector<uint64_t> sums(4 * K + 4);
+    std::vector<uint32_t> best(2 * K), slot(4 * m1), node(2 * N);
+    r.community.resize(m1);
+    d_sums.Read(queue_, 4 * K + 4, sums.data());
+    d_best.Read(queue_, 2 * K, best.data());
+    d_slot.Read(queue_, 4 * m1, slot.data());
+    d_comm.Read(queue_, m1, r.community.data());
+    d_node.Read(queue_, 2 * N, node.data());
+    queue_.Finish();
+    r.community.resize(M);
+    r.root.assign(slot.begin() + 2 * m1, slot.begin() + 2 * m1 + M);
+    r.size.assign(slot.begin() + 3 * m1, slot.begin() + 3 * m1 + M);
+    r.stray.assign(node.begin() + N, node.end());
+    r.members.assign(sums.begin(), sums.begin() + K);
+    r.components.assign(sums.begin() + K, sums.begin() + 2 * K);
+    r.singletons.assign(sums.begin() + 2 * K, sums.begin() + 3 * K);
+    r.largest.assign(best.begin(), best.begin() + K);
+    for (uint64_t k = 0; k < K; ++k) r.largest_root[k] = static_cast<int32_t>(best[K + k]);
+    r.links = sums[4 * K];
+    r.skipped = sums[4 * K + 1];
+    r.shared = sums[4 * K + 2];
+    if (sums[4 * K + 3] != 0)
+      throw std::runtime_error("CommunityComponents: " + std::to_string(sums[4 * K + 3]) +
+                               " finds or hooks took more than 2^20 steps and were given up");
+  }
+  r.Derive();
+}
+
+bool Learner::WriteCommunityComponents(std::ostream* out, Float threshold, const std::vector<Edge>* edges) {
+  ComponentsResult r;
+  CommunityComponents(threshold, &r, edges);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.links + r.skipped << " " << r.root.size() << " " << G9(threshold)
+       << " " << r.skipped << " " << r.shared << "\n";
+  for (size_t k = 0; k < r.members.size(); ++k)
+    *out << "c " << k << " " << r.members[k] << " " << r.components[k] << " " << r.largest[k] << " " << r.largest_root[k] << " "
+         << r.singletons[k] << "\n";
+  for (size_t a = 0; a + 1 < r.offsets.size(); ++a) {
+    *out << "n " << a << " " << r.offsets[a + 1] - r.offsets[a];
+    for (uint64_t s = r.offsets[a]; s < r.offsets[a + 1]; ++s) *out << " " << r.community[s] << " " << r.root[s] << " " << r.size[s];
+    *out << "\n";
+  }
   return static_cast<bool>(*out);
 }
 

@@ -1563,6 +1563,117 @@ class Triangles:
         return self.tr.last_kernel_name()
 
 
+class CommunityComponents:
+    """The connected components of every detected community (include/ammsb_components.h): over CommunityLinks' node-major
+    membership bits, the memberships are numbered ("slots": node by node, communities ascending), an edge pass unites the
+    two slots of every community both ends of a key share in a lock-free union-find, and a finish pass reduces the forest
+    to the root and size per slot, the counts per community and the stray memberships per node.  Integers that the
+    partition alone determines: exact, and independent of the kernel form, the order of the keys and how the list is cut
+    into calls.  Owns nothing but the tensors it returns."""
+
+    PER_COMMUNITY = (("members", torch.int64), ("components", torch.int64), ("singletons", torch.int64), ("best", torch.int64),
+                     ("largest", torch.int32), ("largest_root", torch.int32))
+    PER_SLOT = (("slot_node", torch.int32), ("slot_comm", torch.int16), ("parent", torch.int32), ("root", torch.int32),
+                ("size", torch.int32))
+
+    def __init__(self, ctx):
+        from . import _components
+        self.ctx = ctx
+        self.cc = _components
+        self.lib = _components.load()
+        self.links = CommunityLinks(ctx)
+
+    def _mask(self, mask, N, K):
+        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
+            raise AmmsbError("components: not the mask of a %d x %d pi" % (N, K))
+
+    def own(self, mask, N, K):
+        """-> own [N] int32 (uint32 bits): the memberships of every node"""
+        N, K = int(N), int(K)
+        self._mask(mask, N, K)
+        own = self.ctx.empty((N,), torch.int32)
+        if N:
+            self.cc.check(self.lib.ammsb_components_own(_ptr(mask), N, K, _ptr(own), _stream()))
+        return own
+
+    def base(self, own, threshold=None):
+        """own -> (base [N + 1] int64, the exclusive prefix sum by a torch cumsum in int64, M = base[N]); waits for M and
+        refuses M >= 2^32"""
+        base = torch.zeros(own.numel() + 1, dtype=torch.int64, device=own.device)
+        if own.numel():
+            torch.cumsum(own.to(torch.int64) & 0xFFFFFFFF, 0, out=base[1:])
+        return base, self.cc.check_slots(int(base[-1]), threshold)
+
+    def state(self, N, K, M):
+        """-> the buffers of one run for an N x K pi with M slots: name -> device tensor (uint32 as int32, uint16 as int16,
+        uint64 as int64); slot_node, slot_comm, parent, root, size [M]; members, components, singletons, best, largest,
+        largest_root [K]; stray [N]; counts [4] (valid, skipped, shared, give-ups).  What the library adds to is zeroed."""
+        out = {name: self.ctx.empty((M,), dtype) for name, dtype in self.PER_SLOT}
+        out.update({name: self.ctx.zeros((K,), dtype) for name, dtype in self.PER_COMMUNITY})
+        out["stray"] = self.ctx.zeros((N,), torch.int32)
+        out["counts"] = self.ctx.zeros((4,), torch.int64)
+        return out
+
+    def _check(self, mask, N, K, base, M, state):
+        self._mask(mask, N, K)
+        if base.dtype != torch.int64 or not base.is_contiguous() or base.numel() != N + 1:
+            raise AmmsbError("components: base must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
+        for names, n in ((self.PER_SLOT, M), (self.PER_COMMUNITY, K), ((("stray", torch.int32),), N), ((("counts", torch.int64),), 4)):
+            for name, dtype in names:
+                t = state[name]
+                if t.dtype != dtype or not t.is_contiguous() or t.numel() != n:
+                    raise AmmsbError("components: %s of the state does not fit N = %d, K = %d, M = %d" % (name, N, K, M))
+
+    def slots(self, mask, N, K, base, M, state, first=0, count=None):
+        """numbers the slots of the nodes first .. first + count - 1 (default: through N - 1): slot_node, slot_comm and
+        parent[s] = s of the state -> state"""
+        N, K, M, first = int(N), int(K), self.cc.check_slots(M), int(first)
+        count = N - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > N:
+            raise AmmsbError("components: the nodes %d .. %d are not inside 0 .. %d" % (first, first + count, N))
+        self._check(mask, N, K, base, M, state)
+        if count and M:
+            self.cc.check(self.lib.ammsb_components_slots(_ptr(mask), N, K, _ptr(base), M, first, count, _ptr(state["slot_node"]),
+                                                          _ptr(state["slot_comm"]), _ptr(state["parent"]), _stream()))
+        return state
+
+    def edges(self, mask, N, K, base, M, edges, state):
+        """edges: keys (a << 32) | b, a host array or a contiguous 1-d int64 (uint64 bits) device tensor, fewer than 2^31.
+        Unites the slots they join in parent and adds to counts; any number of calls on pieces of the list -> state"""
+        edges = _edge_keys(self.ctx, edges, "components")
+        N, K, M, n = int(N), int(K), self.cc.check_slots(M), self.cc.check_keys(edges.numel())
+        self._check(mask, N, K, base, M, state)
+        if n:  # (an empty list is a valid no-op; its empty tensor has no address)
+            self.cc.check(self.lib.ammsb_components_edges(_ptr(mask) if N else None, N, K, _ptr(base), M, _ptr(edges), n,
+                                                          _ptr(state["parent"]) if M else None, _ptr(state["counts"]), _stream()))
+        return state
+
+    def finish(self, N, K, base, M, state):
+        """after the last edges(): root and size per slot, the K-sized arrays and stray of the state -> state"""
+        N, K, M = int(N), int(K), self.cc.check_slots(M)
+        slot = lambda name: _ptr(state[name]) if M else None   # noqa: E731  (an empty tensor has no address)
+        self.cc.check(self.lib.ammsb_components_finish(
+            N, K, _ptr(base), M, slot("slot_node"), slot("slot_comm"), slot("parent"), slot("root"), slot("size"),
+            _ptr(state["members"]), _ptr(state["components"]), _ptr(state["singletons"]), _ptr(state["best"]),
+            _ptr(state["largest"]), _ptr(state["largest_root"]), _ptr(state["stray"]) if N else None, _ptr(state["counts"]),
+            _stream()))
+        return state
+
+    def run(self, pi, thr, edges, mask=None):
+        """-> (state, base, M) for the cover (pi, thr) and the edge list"""
+        N, K = int(pi.desc.num_rows), int(pi.cols)
+        thr = self.cc.check_threshold(thr)
+        mask = self.links.mask(pi, thr) if mask is None else mask
+        base, M = self.base(self.own(mask, N, K), thr)
+        state = self.state(N, K, M)
+        self.slots(mask, N, K, base, M, state)
+        self.edges(mask, N, K, base, M, edges, state)
+        return self.finish(N, K, base, M, state), base, M
+
+    def kernel_name(self):
+        return self.cc.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

@@ -1,6 +1,6 @@
 """The post-fit analyses of a Learner: what reads a fitted model out -- memberships and communities, link prediction,
 link communities, community quality, the three comparisons with a ground-truth cover (F1 match, overlapping NMI, Omega
-index), how the detected communities relate to each other, how they are linked, the overlapping modularity of the cover, the role of every node in it and the triangles inside the communities.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
+index), how the detected communities relate to each other, how they are linked, the overlapping modularity of the cover, the role of every node in it, the triangles inside the communities and the connected components of each.  Each drives one ops class over (pi, beta) as they stand: drained first, local on any rank (every rank
 holds all of pi, so none is a collective), and nothing of the iteration is touched -- no RNG stream, no counter, no
 buffer.  There is no CPU path: without a device every one of them raises."""
 import numpy as np
@@ -552,3 +552,31 @@ class PostFit:
         return _triangles.Triangles(threshold, part(rs, "degree"), part(st, "tri"), part(st, "tri_in"), part(st, "tri_comms"),
                                     whole(st, "ktri3"), whole(st, "kpart"), whole(rs, "kmembers"), (ksq - ksum) // np.uint64(2),
                                     M, skipped, dropped, N=N, first=first)
+
+    # ---- is each community one piece? (include/ammsb_components.h)
+    def _components(self):
+        return self._postfit_op("_components_op", "CommunityComponents", "the community components")
+
+    def CommunityComponents(self, threshold=0.05, edges=None):
+        """-> _components.Components: the connected components of every community of the cover pi[a, k] >= threshold inside
+        the graph of `edges` (host array or device tensor of (a << 32) | b, either order of the ends, duplicates and a == a
+        valid, a key with an end >= N counted in .skipped; default: TrainingLinks()), fewer than 2^31 keys: two members of k
+        are connected iff a path of keys joins them through members of k.  .members, .components, .largest, .largest_root,
+        .singletons per community; the memberships as a CSR over the nodes, .offsets [N + 1] and .community, .root, .size [M]
+        (the root of a component is its smallest node); .stray [N], the memberships outside their community's largest
+        component; .links, .skipped, .shared, .M, all exact integers; .giant, .fragmentation [K] and .connected in float64 on
+        the host; .disconnected(), .cover(), .trimmed().  A cover of 2^32 memberships or more is refused."""
+        from . import _components
+        threshold = _components.check_threshold(threshold)
+        op = self._components()
+        self.drain()
+        edges = self._linkcomm_edges(edges)
+        _components.check_keys(edges.numel())
+        st, base, M = op.run(self.pi, threshold, edges)
+        valid, skipped, shared, giveups = (int(v) for v in st["counts"].cpu().numpy().view(np.uint64))
+        _components.check_giveups(giveups)
+        h = lambda name, dt: st[name].cpu().numpy().view(dt)   # noqa: E731
+        return _components.Components(threshold, h("members", np.uint64), h("components", np.uint64), h("largest", np.uint32),
+                                      h("largest_root", np.int32), h("singletons", np.uint64), base.cpu().numpy().view(np.uint64),
+                                      h("slot_comm", np.uint16), h("root", np.uint32), h("size", np.uint32), h("stray", np.uint32),
+                                      valid, skipped, shared)
