@@ -23,8 +23,8 @@
 //   bounded loops  a find or hook that takes more than MAX_STEPS = 2^20 steps stops, counts[3] += 1, and that union stays
 //                  undone; the hosts raise on it.
 //
-// The kernels clear the bits past K of every word they read, and no slot >= num_slots or community >= K is used as an
-// index: the mask and base are public buffers.
+// The mask is read through mask_word() of ammsb_postfit.h alone (bits past K cleared), and no slot >= num_slots or
+// community >= K is used as an index: the mask and base are public buffers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -71,16 +71,6 @@ struct Finish {
   u64* counts;
 };
 
-// the bits of word w that stand for a community
-__device__ __forceinline__ u64 live_bits(uint32_t w, uint32_t K) {
-  const uint32_t left = K - 64u * w;  // (w < W: > 0)
-  return left >= 64u ? ~0ull : (1ull << left) - 1ull;
-}
-
-__device__ __forceinline__ u64 mask_word(const Args& a, uint32_t node, uint32_t w) {
-  return w < a.W ? a.mask[(uint64_t)node * a.W + w] & live_bits(w, a.K) : 0ull;
-}
-
 // the sum of v over the lanes of a group of G
 __device__ __forceinline__ uint32_t group_sum(uint32_t v, uint32_t G) {
   for (uint32_t o = G >> 1; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, (int)o, 64);  // o < G: stays inside the group
@@ -95,15 +85,6 @@ __device__ __forceinline__ uint32_t group_before(uint32_t v, uint32_t G, uint32_
     if (gl >= o) inc += t;  // (a lane nearer than o to its group's start takes nothing from the group before)
   }
   return inc - v;
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
-    v += ((u64)hi << 32) | lo;
-  }
-  return v;
 }
 
 // ------------------------------------------------------------------------------------------ the union-find
@@ -359,7 +340,6 @@ __global__ __launch_bounds__(C_BLOCK) void components_finish_stray(Finish f) {
 }
 
 // ------------------------------------------------------------------------------------------ host
-bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
 
 const char* check_shape(uint64_t num_rows, uint32_t K, uint64_t num_slots) {
   if (K == 0 || K > AMMSB_COMPONENTS_MAX_COLS) return "num_cols outside 1..8192";

@@ -18,8 +18,8 @@
 //   connect_finish        links = directed + directed^T.
 //   connect_top           ammsb_relate.hip's relate_top over 64-bit link counts and the pair counts d_k d_l - overlap.
 //
-// The edge kernels clear the bits past K of every word they read: the mask is a public buffer, and a set bit that stands
-// for no community would be a cell outside directed.
+// The mask's layout, and the rule that its readers (the edge kernels here among them) clear the bits past K, are stated
+// once, in ammsb_postfit.h.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -61,12 +61,6 @@ struct MaskArgs {
   float thr;
   u64* mask;
 };
-
-__device__ __forceinline__ void store_row(const MaskArgs& a, uint64_t row, uint32_t W, u64 w0, u64 w1, int lane) {
-  u64* out = a.mask + row * W;
-  if ((uint32_t)lane < W) out[lane] = w0;
-  if ((uint32_t)lane + 64u < W) out[lane + 64] = w1;
-}
 
 // bit j of the low 16 -> bit 4 j
 __device__ __forceinline__ u64 spread4(u64 x) {
@@ -113,7 +107,7 @@ __global__ __launch_bounds__(C_BLOCK) void connect_mask_fast(MaskArgs a) {
         else w1 = word;
       }
     }
-    store_row(a, r, W, w0, w1, lane);
+    store_bit_row(a.mask, r, W, w0, w1, lane);
   }
 }
 
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(C_BLOCK) void connect_mask_generic(MaskArgs a) {
       const float v = col < K ? p[col] : -1.0f;  // (below every threshold)
       place(w0, w1, t, __ballot(v >= a.thr), lane);
     }
-    store_row(a, r, W, w0, w1, lane);
+    store_bit_row(a.mask, r, W, w0, w1, lane);
   }
 }
 
@@ -148,16 +142,6 @@ struct EdgeArgs {
   u64* directed;
   u64* counts;
 };
-
-// the bits of word w that stand for a community
-__device__ __forceinline__ u64 live_bits(uint32_t w, uint32_t K) {
-  const uint32_t left = K - 64u * w;  // (w < W: > 0)
-  return left >= 64u ? ~0ull : (1ull << left) - 1ull;
-}
-
-__device__ __forceinline__ u64 mask_word(const EdgeArgs& a, uint32_t node, uint32_t w) {
-  return w < a.W ? a.mask[(uint64_t)node * a.W + w] & live_bits(w, a.K) : 0ull;
-}
 
 // every lane's exclusive prefix sum of v over the wave, and the sum
 __device__ __forceinline__ uint32_t wave_prefix(uint32_t v, int lane, uint32_t* total) {

@@ -15,8 +15,7 @@
 // the carry (old + low wrapped) where that is not zero.  The low word goes through one sequence of adds whatever their
 // order, so the carries sum to the number of times it wrapped.
 //
-// The kernels clear the bits past K of every word they read: the mask is a public buffer, and a set bit that stands for
-// no community would be an accumulator outside the outputs.
+// The mask is read through mask_word() of ammsb_postfit.h alone (bits past K cleared).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -42,16 +41,6 @@ struct Args {
   u64* acc;          // edges: internal; nodes: volume
   u64* counts;
 };
-
-// the bits of word w that stand for a community
-__device__ __forceinline__ u64 live_bits(uint32_t w, uint32_t K) {
-  const uint32_t left = K - 64u * w;  // (w < W: > 0)
-  return left >= 64u ? ~0ull : (1ull << left) - 1ull;
-}
-
-__device__ __forceinline__ u64 mask_word(const Args& a, uint32_t node, uint32_t w) {
-  return w < a.W ? a.mask[(uint64_t)node * a.W + w] & live_bits(w, a.K) : 0ull;
-}
 
 // acc[2k], acc[2k + 1] += (hi, lo) modulo 2^128
 __device__ __forceinline__ void add128(u64* acc, uint32_t k, u64 lo, u64 hi) {
@@ -178,7 +167,6 @@ const char* check_shape(uint64_t num_rows, uint32_t K) {
   return nullptr;
 }
 
-bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
 
 void shape(Args* a, const uint64_t* mask, uint64_t num_rows, uint32_t num_cols) {
   a->mask = reinterpret_cast<const u64*>(mask);

@@ -126,12 +126,6 @@ struct TruthArgs {
   u64 *skipped, *outside;
 };
 
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(O_BLOCK) void omega_truth_scatter(TruthArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
   const u64 stride = (u64)gridDim.x * O_WAVES;

@@ -1,7 +1,8 @@
-// What the libraries that read a fitted model share (libammsb_readout / _linkpred / _linkcomm / _quality / _cover / _nmi /
-// _omega .so): the descriptor check that decides whether a kernel may issue 16-byte loads, the per-thread error and
-// launch state, the wave-wide selection the exactness claims of DESIGN 4.8 and 4.10 rest on, the block-private
-// counters, the row addressing, and the slot -> column rule of the kernels that read a row either way.
+// What every one-object library of csrc/Makefile's ONE shares, refsample alone excepted (it reads no fitted model):
+// the descriptor check that decides whether a kernel may issue 16-byte loads, the per-thread error and launch state,
+// the wave-wide selection the exactness claims of DESIGN 4.8 and 4.10 rest on, the block-private counters, the row
+// addressing, the slot -> column rule of the kernels that read a row either way, and the readers and writers of the
+// node-major membership bits that libammsb_connect.so's mask pass makes and five libraries read.
 //
 // Everything here has internal linkage on purpose (an unnamed namespace; device code is __forceinline__): each
 // library is one translation unit, keeps thread_local state of its own and exports nothing but what its header
@@ -91,6 +92,9 @@ const char* check_rpm(const ammsb_rpm* m, uint64_t max_cols, bool* aligned16) {
   return nullptr;
 }
 
+// p is not a multiple of `to` bytes (a power of two)
+bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
+
 // ------------------------------------------------------------------------------------------ wave reductions
 // Every lane ends with the maximum.  Lanes 0..15 of each row of 16 by DPP (two quad permutes, then the mirrors pair
 // quads and halves: a max does not care which partner it meets, only that the groups merge), rows by two shuffles.
@@ -117,7 +121,47 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   return v;
 }
 
+// every lane ends with the sum
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 __device__ __forceinline__ float comp(const float4& q, int c) { return c == 0 ? q.x : c == 1 ? q.y : c == 2 ? q.z : q.w; }
+
+// ------------------------------------------------------------------------------------------ node-major membership bits
+// Row a of the mask is W = ceil(K / 64) 64-bit words; bit k & 63 of word k >> 6 says pi[a, k] >= thr.  connect_mask_* of
+// ammsb_connect.hip write it; the edge kernels of connect and the kernels of modularity, roles, triangles and components
+// read it, through mask_word() alone.
+//
+// Bits past K are cleared on read.  The mask is a public buffer, so a reader does not trust the last word of a row: a
+// set bit that stands for no community would become an index outside whatever the kernel keeps per community (a cell
+// of directed, an accumulator, a counter of ksum / ksq / kmembers or ktri3 / kpart, a slot's community).  A kernel that
+// turns a bit of mask_word() into a community k may therefore rely on k < K, which the "(< K: live_bits)" remarks at
+// those places refer to.
+
+// the bits of word w that stand for a community
+__device__ __forceinline__ unsigned long long live_bits(uint32_t w, uint32_t K) {
+  const uint32_t left = K - 64u * w;  // (w < W: > 0)
+  return left >= 64u ? ~0ull : (1ull << left) - 1ull;
+}
+
+// Word w of node's row, 0 past the row.  `a` is the kernel's own argument struct (each has mask, W and K), not three
+// scalars, so that every kernel loads those fields where it did when it had this function to itself.
+template <class Args>
+__device__ __forceinline__ unsigned long long mask_word(const Args& a, uint32_t node, uint32_t w) {
+  return w < a.W ? a.mask[(uint64_t)node * a.W + w] & live_bits(w, a.K) : 0ull;
+}
+
+// A wave writes row `row` of W <= 128 words: lane l holds words l (w0) and l + 64 (w1), as place() left them.  The mask
+// passes of quality and connect end with it (their words differ, the way they reach memory does not).
+__device__ __forceinline__ void store_bit_row(unsigned long long* out_base, uint64_t row, uint32_t W, unsigned long long w0,
+                                              unsigned long long w1, int lane) {
+  unsigned long long* out = out_base + row * W;
+  if ((uint32_t)lane < W) out[lane] = w0;
+  if ((uint32_t)lane + 64u < W) out[lane + 64] = w1;
+}
 
 // ------------------------------------------------------------------------------------------ selection
 // A round of "the T largest (value, lowest column first)": every lane's best eligible element, the wave maximum of the

@@ -36,12 +36,6 @@ struct MaskArgs {
   u64* mask;
 };
 
-__device__ __forceinline__ void store_row(const MaskArgs& a, uint64_t row, uint32_t W, u64 w0, u64 w1, int lane) {
-  u64* out = a.mask + row * W;
-  if ((uint32_t)lane < W) out[lane] = w0;
-  if ((uint32_t)lane + 64u < W) out[lane + 64] = w1;
-}
-
 // up to 4 float4 per lane: columns 1024 ch + 256 i + 4 lane + c of the row; registers past the row hold -1, which is
 // below every threshold the entry point lets through
 __device__ __forceinline__ void load_chunk(const MaskArgs& a, uint32_t row, int ch, int nvK, int lane, float4 (&x)[4]) {
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(Q_BLOCK) void quality_mask_fast(MaskArgs a) {
 #pragma unroll
       for (int t = 0; t < 16; ++t) place(w0, w1, 16u * ch + t, b[t], lane);
     }
-    store_row(a, r, W, w0, w1, lane);
+    store_bit_row(a.mask, r, W, w0, w1, lane);
   }
 }
 
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(Q_BLOCK) void quality_mask_generic(MaskArgs a) {
       const float v = col < K ? p[col] : -1.0f;
       place(w0, w1, t, __ballot(v >= a.thr), lane);
     }
-    store_row(a, r, W, w0, w1, lane);
+    store_bit_row(a.mask, r, W, w0, w1, lane);
   }
 }
 

@@ -21,8 +21,8 @@
 // Rows go to the waves of a persistent grid in turn (wave g takes rows g, g + G, ...).  A hub row is walked by its one
 // wave.
 //
-// The kernel clears the bits past K of every word it reads: the mask is a public buffer, and a set bit that stands for no
-// community would be a counter outside ktri3 / kpart.  Every index into the mask (a W) and into targets is 64-bit.
+// The mask is read through mask_word() of ammsb_postfit.h alone (bits past K cleared).  Every index into the mask (a W)
+// and into targets is 64-bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -48,16 +48,6 @@ struct Args {
   uint32_t *tri, *tri_in, *tri_comms;
   u64 *ktri3, *kpart, *counts;
 };
-
-// the bits of word w that stand for a community
-__device__ __forceinline__ u64 live_bits(uint32_t w, uint32_t K) {
-  const uint32_t left = K - 64u * w;  // (w < W: > 0)
-  return left >= 64u ? ~0ull : (1ull << left) - 1ull;
-}
-
-__device__ __forceinline__ u64 mask_word(const Args& a, uint32_t node, uint32_t w) {
-  return w < a.W ? a.mask[(uint64_t)node * a.W + w] & live_bits(w, a.K) : 0ull;
-}
 
 // every lane ends with the sum
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
@@ -240,7 +230,6 @@ __device__ __forceinline__ void nodes_body(const Args& a) {
 __global__ __launch_bounds__(64 * W1_WAVES) void triangles_nodes_w1(Args a) { nodes_body<1, W1_WAVES>(a); }
 __global__ __launch_bounds__(64 * W2_WAVES) void triangles_nodes_w2(Args a) { nodes_body<2, W2_WAVES>(a); }
 
-bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
 
 }  // namespace
 

@@ -74,6 +74,25 @@ std::string Num(double x, int digits) {
 }
 std::string G9(double x) { return Num(x, 9); }
 std::string G17(double x) { return Num(x, 17); }
+
+// bytes of device memory set to zero on the stream, for the analysis `who`
+void Zero(const char* who, void* p, uint64_t bytes, hipStream_t stream) {
+  const hipError_t e = hipMemsetAsync(p, 0, bytes, stream);
+  if (e != hipSuccess) throw std::runtime_error(std::string(who) + ": memset: " + hipGetErrorString(e));
+}
+
+// The node-major membership bits pi[a, k] >= threshold (libammsb_connect.so's mask) in a buffer of their own, filled on
+// the stream; a failure is reported under the name `call`.  fill = false only allocates (a buffer needs a byte).
+clcuda::Buffer<uint64_t> MembershipMask(const char* call, const ammsb_rpm* pi, Float threshold,
+                                        const clcuda::Context& context, hipStream_t stream, bool fill = true) {
+  const uint64_t words = ammsb_connect_mask_bytes(pi->num_rows, static_cast<uint32_t>(pi->num_cols)) / sizeof(uint64_t);
+  clcuda::Buffer<uint64_t> d_mask(context, std::max<uint64_t>(words, 1));
+  if (fill) {
+    const int rc = ammsb_connect_mask(pi, threshold, d_mask(), stream);
+    if (rc != AMMSB_OK) throw PostfitError(call, rc, ammsb_connect_last_error());
+  }
+  return d_mask;
+}
 }  // namespace
 
 // ---- reading the model out: libammsb_readout.so over pi, in row slabs whose outputs stay under a fixed byte budget
@@ -228,6 +247,16 @@ std::vector<Edge> SortedTrainingLinks(const Config& cfg) {
   std::sort(links.begin(), links.end());
   links.erase(std::unique(links.begin(), links.end()), links.end());
   return links;
+}
+
+// The edge list an analysis runs over: the caller's, or where it passes none every training link, kept in *training and
+// refused in the analysis's own name from `limit` of them on.
+const std::vector<Edge>* EdgesOrTraining(const char* who, const std::vector<Edge>* edges, const Config& cfg,
+                                         std::vector<Edge>* training, uint64_t limit = ~uint64_t(0)) {
+  if (edges) return edges;
+  *training = SortedTrainingLinks(cfg);
+  if (training->size() >= limit) throw std::invalid_argument(std::string(who) + ": 2^31 training links or more");
+  return training;
 }
 }  // namespace
 
@@ -502,8 +531,7 @@ void Learner::CoverNMI(const std::vector<uint64_t>& offsets, const std::vector<u
                                d_ts(), d_dbest(), d_dover(), d_skipped(), d_dense(), d_ws(), ws_bytes, queue_.stream());
         if (rc != AMMSB_OK) throw PostfitError("ammsb_cover_match", rc, ammsb_cover_last_error());
       } else {  // (the cover match launches nothing for communities without members: their overlap is 0)
-        const hipError_t e = hipMemsetAsync(d_dense(), 0, Gs * K * sizeof(uint32_t), static_cast<hipStream_t>(queue_.stream()));
-        if (e != hipSuccess) throw std::runtime_error(std::string("CoverNMI: memset: ") + hipGetErrorString(e));
+        Zero("CoverNMI", d_dense(), Gs * K * sizeof(uint32_t), static_cast<hipStream_t>(queue_.stream()));
       }
       rc = ammsb_nmi_accumulate(d_dense(), g0, Gs, N, d_tsize(), G, d_dsize(), static_cast<uint32_t>(K), d_HX(), d_HY(),
                                 d_cX(), d_cY(), queue_.stream());
@@ -635,10 +663,9 @@ void Learner::CoverOmega(const std::vector<uint64_t>& offsets, const std::vector
     d_position.Write(queue_, N, position.data());
     d_offsets.Write(queue_, G + 1, offsets.data());
     if (M) d_members.Write(queue_, M, members.data());
-    hipError_t e = hipMemsetAsync(d_tbits(), 0, std::max<uint64_t>(n * WT, 1) * sizeof(uint32_t), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tcount(), 0, n * sizeof(uint32_t), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tally(), 0, 2 * sizeof(uint64_t), stream);
-    if (e != hipSuccess) throw std::runtime_error(std::string("CoverOmega: memset: ") + hipGetErrorString(e));
+    Zero("CoverOmega", d_tbits(), std::max<uint64_t>(n * WT, 1) * sizeof(uint32_t), stream);
+    Zero("CoverOmega", d_tcount(), n * sizeof(uint32_t), stream);
+    Zero("CoverOmega", d_tally(), 2 * sizeof(uint64_t), stream);
     int rc = ammsb_omega_detected_bits(&pi_->Get(), threshold, d_nodes(), n, d_dbits(), d_dcount(), stream);
     if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_detected_bits", rc, ammsb_omega_last_error());
     rc = ammsb_omega_truth_bits(d_offsets(), G, d_members(), M, N, d_position(), n, d_tbits(), d_tcount(), d_tally(),
@@ -657,8 +684,7 @@ void Learner::CoverOmega(const std::vector<uint64_t>& offsets, const std::vector
     if (L > AMMSB_OMEGA_MAX_LEVELS) throw std::runtime_error("CoverOmega: a node of the universe is in more than 4095 communities");
     hist.assign(3 * L + 1, 0);
     clcuda::Buffer<uint64_t> d_hist(context, 3 * L + 1);
-    e = hipMemsetAsync(d_hist(), 0, (3 * L + 1) * sizeof(uint64_t), stream);
-    if (e != hipSuccess) throw std::runtime_error(std::string("CoverOmega: memset: ") + hipGetErrorString(e));
+    Zero("CoverOmega", d_hist(), (3 * L + 1) * sizeof(uint64_t), stream);
     const uint64_t R = (n + AMMSB_OMEGA_TILE - 1) / AMMSB_OMEGA_TILE, total = R * (R + 1) / 2;
     const uint64_t step = std::min<uint64_t>(
         AMMSB_OMEGA_MAX_LAUNCH_TILES, std::max<uint64_t>(1, launch_pairs / (uint64_t(AMMSB_OMEGA_TILE) * AMMSB_OMEGA_TILE)));
@@ -705,8 +731,7 @@ void OverlapOnDevice(const ammsb_rpm* pi, Float threshold, uint64_t max_bytes, c
                      const clcuda::Context& context, void* stream) {
   const uint64_t N = pi->num_rows, K = pi->num_cols;
   if (K == 0 || K > AMMSB_RELATE_MAX_COLS) throw std::runtime_error("CommunityOverlap: K outside 1..8192");
-  hipError_t e = hipMemsetAsync((*d_overlap)(), 0, K * K * sizeof(uint32_t), static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) throw std::runtime_error(std::string("CommunityOverlap: memset: ") + hipGetErrorString(e));
+  Zero("CommunityOverlap", (*d_overlap)(), K * K * sizeof(uint32_t), static_cast<hipStream_t>(stream));
   if (N == 0) return;
   const uint64_t step = std::min<uint64_t>((N + 63) / 64 * 64, std::max<uint64_t>(64, max_bytes * 8 / K / 64 * 64));
   clcuda::Buffer<uint64_t> d_bits(context, K * (step / 64));
@@ -717,7 +742,7 @@ void OverlapOnDevice(const ammsb_rpm* pi, Float threshold, uint64_t max_bytes, c
     if (rc != AMMSB_OK) throw PostfitError("ammsb_relate", rc, ammsb_relate_last_error());
   }
   // d_bits is freed on return: the slabs have to be through with it
-  e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
+  const hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
   if (e != hipSuccess) throw std::runtime_error(std::string("CommunityOverlap: ") + hipGetErrorString(e));
 }
 }  // namespace
@@ -794,23 +819,20 @@ void LinksOnDevice(const ammsb_rpm* pi, Float threshold, const std::vector<Edge>
   if (K == 0 || K > AMMSB_CONNECT_MAX_COLS) throw std::runtime_error("CommunityLinks: K outside 1..8192");
   hipStream_t stream = static_cast<hipStream_t>(queue.stream());
   clcuda::Buffer<uint64_t> d_directed(context, K * K);
-  hipError_t e = hipMemsetAsync(d_directed(), 0, K * K * sizeof(uint64_t), stream);
-  if (e == hipSuccess) e = hipMemsetAsync((*d_counts)(), 0, 2 * sizeof(uint64_t), stream);
-  if (e != hipSuccess) throw std::runtime_error(std::string("CommunityLinks: memset: ") + hipGetErrorString(e));
-  const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
-  clcuda::Buffer<uint64_t> d_mask(context, std::max<uint64_t>(words, 1));
+  Zero("CommunityLinks", d_directed(), K * K * sizeof(uint64_t), stream);
+  Zero("CommunityLinks", (*d_counts)(), 2 * sizeof(uint64_t), stream);
+  // without an edge or a node the mask is not made and no edge kernel runs (the keys are uploaded before the mask pass)
+  const bool any = !edges.empty() && N > 0;
   std::unique_ptr<clcuda::Buffer<Edge>> d_edges;
+  if (any) d_edges.reset(new clcuda::Buffer<Edge>(context, queue, edges.begin(), edges.end()));
+  const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect", pi, threshold, context, stream, any);
   int rc = AMMSB_OK;
-  if (!edges.empty() && N > 0) {
-    d_edges.reset(new clcuda::Buffer<Edge>(context, queue, edges.begin(), edges.end()));
-    rc = ammsb_connect_mask(pi, threshold, d_mask(), stream);
-    if (rc == AMMSB_OK)
-      rc = ammsb_connect_edges(d_mask(), N, static_cast<uint32_t>(K), (*d_edges)(), edges.size(), d_directed(),
-                               (*d_counts)(), stream);
-  }
+  if (any)
+    rc = ammsb_connect_edges(d_mask(), N, static_cast<uint32_t>(K), (*d_edges)(), edges.size(), d_directed(), (*d_counts)(),
+                             stream);
   if (rc == AMMSB_OK) rc = ammsb_connect_finish(d_directed(), static_cast<uint32_t>(K), (*d_links)(), stream);
   if (rc != AMMSB_OK) throw PostfitError("ammsb_connect", rc, ammsb_connect_last_error());
-  e = hipStreamSynchronize(stream);
+  const hipError_t e = hipStreamSynchronize(stream);
   if (e != hipSuccess) throw std::runtime_error(std::string("CommunityLinks: ") + hipGetErrorString(e));
 }
 }  // namespace
@@ -920,11 +942,7 @@ void Learner::Modularity(Float threshold, const std::vector<Edge>* edges, Modula
   const uint64_t N = pi_->Rows(), K = pi_->Cols();
   if (K == 0 || K > AMMSB_MODULARITY_MAX_COLS) throw std::runtime_error("Modularity: K outside 1..8192");
   std::vector<Edge> training;
-  if (!edges) {
-    training = SortedTrainingLinks(cfg_);
-    if (training.size() >= AMMSB_MODULARITY_MAX_EDGES) throw std::invalid_argument("Modularity: 2^31 training links or more");
-    edges = &training;
-  }
+  edges = EdgesOrTraining("Modularity", edges, cfg_, &training, AMMSB_MODULARITY_MAX_EDGES);
   result->internal.assign(K, 0);
   result->volume.assign(K, 0);
   result->degree.assign(N, 0);
@@ -933,16 +951,13 @@ void Learner::Modularity(Float threshold, const std::vector<Edge>* edges, Modula
   if (!edges->empty() && N > 0) {
     hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
     const clcuda::Context context = queue_.GetContext();
-    const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
-    clcuda::Buffer<uint64_t> d_mask(context, words), d_sums(context, 4 * K + 2);  // internal, volume, counts
+    clcuda::Buffer<uint64_t> d_sums(context, 4 * K + 2);  // internal, volume, counts
     clcuda::Buffer<uint32_t> d_degree(context, N);
     clcuda::Buffer<Edge> d_edges(context, queue_, edges->begin(), edges->end());
-    hipError_t e = hipMemsetAsync(d_sums(), 0, (4 * K + 2) * sizeof(uint64_t), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_degree(), 0, N * sizeof(uint32_t), stream);
-    if (e != hipSuccess) throw std::runtime_error(std::string("Modularity: memset: ") + hipGetErrorString(e));
-    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
-    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
-    rc = ammsb_modularity_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), edges->size(), d_degree(), d_sums(),
+    Zero("Modularity", d_sums(), (4 * K + 2) * sizeof(uint64_t), stream);
+    Zero("Modularity", d_degree(), N * sizeof(uint32_t), stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    int rc = ammsb_modularity_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), edges->size(), d_degree(), d_sums(),
                                 d_sums() + 4 * K, stream);
     if (rc == AMMSB_OK)
       rc = ammsb_modularity_nodes(d_mask(), N, static_cast<uint32_t>(K), d_degree(), d_sums() + 2 * K, stream);
@@ -1071,17 +1086,14 @@ void Learner::NodeRoles(Float threshold, const std::vector<Edge>* edges, uint32_
   if (N > 0) {
     hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
     const clcuda::Context context = queue_.GetContext();
-    const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
     if (targets.empty()) targets.push_back(0);  // (a buffer needs a byte; no offset reaches it)
-    clcuda::Buffer<uint64_t> d_mask(context, words), d_sums(context, 3 * K + 2), d_wide(context, 2 * N);  // ksum ksq kmembers counts; votes squares
+    clcuda::Buffer<uint64_t> d_sums(context, 3 * K + 2), d_wide(context, 2 * N);  // ksum ksq kmembers counts; votes squares
     clcuda::Buffer<uint32_t> d_node(context, 5 * N), d_slots(context, 2 * N * top);  // degree own embedded reached hflags; home hcount
     clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
     clcuda::Buffer<Vertex> d_targets(context, queue_, targets.begin(), targets.end());
-    const hipError_t e = hipMemsetAsync(d_sums(), 0, (3 * K + 2) * sizeof(uint64_t), stream);
-    if (e != hipSuccess) throw std::runtime_error(std::string("NodeRoles: memset: ") + hipGetErrorString(e));
-    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
-    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
-    rc = ammsb_roles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N,
+    Zero("NodeRoles", d_sums(), (3 * K + 2) * sizeof(uint64_t), stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    int rc = ammsb_roles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N,
                            among == "own" ? AMMSB_ROLES_OWN : AMMSB_ROLES_ALL, top, min_count, d_node(), d_node() + N,
                            d_node() + 2 * N, d_node() + 3 * N, d_wide(), d_wide() + N, reinterpret_cast<int32_t*>(d_slots()),
                            d_slots() + N * top, d_node() + 4 * N, d_sums(), d_sums() + K, d_sums() + 2 * K, d_sums() + 3 * K,
@@ -1179,8 +1191,8 @@ void Learner::Triangles(Float threshold, const std::vector<Edge>* edges, Triangl
   const uint64_t N = pi_->Rows(), K = pi_->Cols();
   if (K == 0 || K > AMMSB_TRIANGLES_MAX_COLS) throw std::runtime_error("Triangles: K outside 1..8192");
   // the simple adjacency: both directions of every valid key, each row sorted and made unique, loops left out
-  const std::vector<Edge> training = edges ? std::vector<Edge>() : SortedTrainingLinks(cfg_);
-  const std::vector<Edge>& list = edges ? *edges : training;
+  std::vector<Edge> training;
+  const std::vector<Edge>& list = *EdgesOrTraining("Triangles", edges, cfg_, &training);
   std::vector<std::vector<Vertex>> rows(N);
   uint64_t valid = 0, lost = 0;  // keys with both ends < N; with an end >= N
   for (Edge e : list) {
@@ -1219,18 +1231,15 @@ void Learner::Triangles(Float threshold, const std::vector<Edge>* edges, Triangl
   if (N > 0) {
     hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
     const clcuda::Context context = queue_.GetContext();
-    const uint64_t words = ammsb_connect_mask_bytes(N, static_cast<uint32_t>(K)) / sizeof(uint64_t);
     if (targets.empty()) targets.push_back(0);  // (a buffer needs a byte; no offset reaches it)
     // ktri3 kpart counts, then the node roles' ksum ksq kmembers counts; votes squares
-    clcuda::Buffer<uint64_t> d_mask(context, words), d_sums(context, 5 * K + 4), d_wide(context, 2 * N);
+    clcuda::Buffer<uint64_t> d_sums(context, 5 * K + 4), d_wide(context, 2 * N);
     clcuda::Buffer<uint32_t> d_node(context, 7 * N);  // tri tri_in tri_comms; degree own embedded reached
     clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
     clcuda::Buffer<Vertex> d_targets(context, queue_, targets.begin(), targets.end());
-    const hipError_t e = hipMemsetAsync(d_sums(), 0, (5 * K + 4) * sizeof(uint64_t), stream);
-    if (e != hipSuccess) throw std::runtime_error(std::string("Triangles: memset: ") + hipGetErrorString(e));
-    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
-    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
-    rc = ammsb_triangles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N, d_node(), d_node() + N,
+    Zero("Triangles", d_sums(), (5 * K + 4) * sizeof(uint64_t), stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    int rc = ammsb_triangles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N, d_node(), d_node() + N,
                                d_node() + 2 * N, d_sums(), d_sums() + K, d_sums() + 2 * K, stream);
     if (rc != AMMSB_OK) throw PostfitError("ammsb_triangles_nodes", rc, ammsb_triangles_last_error());
     uint64_t* const roles = d_sums() + 2 * K + 2;
@@ -1298,12 +1307,7 @@ void Learner::CommunityComponents(Float threshold, ComponentsResult* result, con
   const uint64_t N = pi_->Rows(), K = pi_->Cols();
   if (K == 0 || K > AMMSB_COMPONENTS_MAX_COLS) throw std::runtime_error("CommunityComponents: K outside 1..8192");
   std::vector<Edge> training;
-  if (!edges) {
-    training = SortedTrainingLinks(cfg_);
-    if (training.size() >= AMMSB_COMPONENTS_MAX_EDGES)
-      throw std::invalid_argument("CommunityComponents: 2^31 training links or more");
-    edges = &training;
-  }
+  edges = EdgesOrTraining("CommunityComponents", edges, cfg_, &training, AMMSB_COMPONENTS_MAX_EDGES);
   ComponentsResult& r = *result;
   r.members.assign(K, 0);
   r.components.assign(K, 0);
@@ -1321,12 +1325,9 @@ void Learner::CommunityComponents(Float threshold, ComponentsResult* result, con
     const uint32_t cols = static_cast<uint32_t>(K);
     hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
     const clcuda::Context context = queue_.GetContext();
-    const uint64_t words = ammsb_connect_mask_bytes(N, cols) / sizeof(uint64_t);
-    clcuda::Buffer<uint64_t> d_mask(context, words);
     clcuda::Buffer<uint32_t> d_node(context, 2 * N);  // own, then stray
-    int rc = ammsb_connect_mask(&pi_->Get(), threshold, d_mask(), stream);
-    if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_mask", rc, ammsb_connect_last_error());
-    rc = ammsb_components_own(d_mask(), N, cols, d_node(), stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    int rc = ammsb_components_own(d_mask(), N, cols, d_node(), stream);
     if (rc != AMMSB_OK) throw PostfitError("ammsb_components_own", rc, ammsb_components_last_error());
     // base: a host prefix sum over the downloaded own
     std::vector<uint32_t> own(N);
@@ -1342,8 +1343,7 @@ void Learner::CommunityComponents(Float threshold, ComponentsResult* result, con
     clcuda::Buffer<uint64_t> d_sums(context, 4 * K + 4);  // members components singletons best; counts
     clcuda::Buffer<uint32_t> d_slot(context, 4 * m1), d_best(context, 2 * K);  // slot_node parent root size; largest largest_root
     clcuda::Buffer<uint16_t> d_comm(context, m1);
-    const hipError_t e = hipMemsetAsync(d_sums(), 0, (4 * K + 4) * sizeof(uint64_t), stream);
-    if (e != hipSuccess) throw std::runtime_error(std::string("CommunityComponents: memset: ") + hipGetErrorString(e));
+    Zero("CommunityComponents", d_sums(), (4 * K + 4) * sizeof(uint64_t), stream);
     uint32_t* const parent = d_slot() + m1;
     uint64_t* const counts = d_sums() + 4 * K;
     if (M > 0) {

@@ -828,6 +828,12 @@ def _u32_vector(ctx, x, what):
     return x
 
 
+def _check_mask(mask, N, K, who):
+    """the node-major membership bits CommunityLinks.mask() makes of an N x K pi: a contiguous int64 [N, ceil(K / 64)]"""
+    if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
+        raise AmmsbError("%s: not the mask of a %d x %d pi" % (who, N, K))
+
+
 class CommunityReadout:
     """The read-out of a fitted pi (include/ammsb_readout.h): per row the T strongest communities with their weights
     (value descending, equal values by column ascending), the number of columns >= thr, and per community the number of
@@ -1292,8 +1298,7 @@ class CommunityLinks:
         [2] int64 (valid, skipped); either is made and zeroed where none is given -> (directed, counts)"""
         edges = _edge_keys(self.ctx, edges, "community links")
         N, K, n = int(N), int(K), int(edges.numel())
-        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
-            raise AmmsbError("community links: not the mask of a %d x %d pi" % (N, K))
+        _check_mask(mask, N, K, "community links")
         directed = self.ctx.zeros((K, K), torch.int64) if directed is None else directed
         counts = self.ctx.zeros((2,), torch.int64) if counts is None else counts
         if directed.dtype != torch.int64 or not directed.is_contiguous() or tuple(directed.shape) != (K, K):
@@ -1350,10 +1355,6 @@ class Modularity:
         self.lib = _modularity.load()
         self.links = CommunityLinks(ctx)
 
-    def _mask(self, mask, N, K):
-        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
-            raise AmmsbError("modularity: not the mask of a %d x %d pi" % (N, K))
-
     def edges(self, mask, N, K, edges, state=None):
         """mask: what CommunityLinks.mask() returned for an N x K pi; edges: keys (a << 32) | b, a host array or a
         contiguous 1-d int64 (uint64 bits) device tensor, fewer than 2^31.  Adds them to state = (degree [N] int32 (uint32
@@ -1361,7 +1362,7 @@ class Modularity:
         -> state"""
         edges = _edge_keys(self.ctx, edges, "modularity")
         N, K, n = int(N), int(K), self.md.check_keys(edges.numel())
-        self._mask(mask, N, K)
+        _check_mask(mask, N, K, "modularity")
         if state is None:
             state = (self.ctx.zeros((N,), torch.int32), self.ctx.zeros((2 * K,), torch.int64), self.ctx.zeros((2,), torch.int64))
         degree, internal, counts = state
@@ -1379,7 +1380,7 @@ class Modularity:
     def nodes(self, mask, N, K, degree):
         """after the last edges(): -> volume [2 K] int64 (uint64 bits)"""
         N, K = int(N), int(K)
-        self._mask(mask, N, K)
+        _check_mask(mask, N, K, "modularity")
         if degree.dtype != torch.int32 or not degree.is_contiguous() or degree.numel() != N:
             raise AmmsbError("modularity: degree must be a contiguous [N] int32 (uint32 bits) device tensor")
         volume = self.ctx.zeros((2 * K,), torch.int64)
@@ -1440,8 +1441,7 @@ class NodeRoles:
         code, min_count = self.rl.check_among(among), self.rl.check_min_count(min_count)
         if top:
             self.rl.check_top(top)
-        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
-            raise AmmsbError("node roles: not the mask of a %d x %d pi" % (N, K))
+        _check_mask(mask, N, K, "node roles")
         if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() != N + 1:
             raise AmmsbError("node roles: offsets must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
         if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 1:
@@ -1529,8 +1529,7 @@ class Triangles:
         made and zeroed where none is given; calls over disjoint ranges fill one state -> state"""
         N, K = int(N), int(K)
         first, count = self.tr.check_nodes((first, N - int(first) if count is None else count), N)
-        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
-            raise AmmsbError("triangles: not the mask of a %d x %d pi" % (N, K))
+        _check_mask(mask, N, K, "triangles")
         if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() != N + 1:
             raise AmmsbError("triangles: offsets must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
         if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 1:
@@ -1583,14 +1582,10 @@ class CommunityComponents:
         self.lib = _components.load()
         self.links = CommunityLinks(ctx)
 
-    def _mask(self, mask, N, K):
-        if mask.dtype != torch.int64 or not mask.is_contiguous() or mask.numel() != N * ((K + 63) // 64):
-            raise AmmsbError("components: not the mask of a %d x %d pi" % (N, K))
-
     def own(self, mask, N, K):
         """-> own [N] int32 (uint32 bits): the memberships of every node"""
         N, K = int(N), int(K)
-        self._mask(mask, N, K)
+        _check_mask(mask, N, K, "components")
         own = self.ctx.empty((N,), torch.int32)
         if N:
             self.cc.check(self.lib.ammsb_components_own(_ptr(mask), N, K, _ptr(own), _stream()))
@@ -1615,7 +1610,7 @@ class CommunityComponents:
         return out
 
     def _check(self, mask, N, K, base, M, state):
-        self._mask(mask, N, K)
+        _check_mask(mask, N, K, "components")
         if base.dtype != torch.int64 or not base.is_contiguous() or base.numel() != N + 1:
             raise AmmsbError("components: base must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
         for names, n in ((self.PER_SLOT, M), (self.PER_COMMUNITY, K), ((("stray", torch.int32),), N), ((("counts", torch.int64),), 4)):
