@@ -9,52 +9,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <fstream>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "ammsb_connect.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
+#include "postfit_test.h"
 
 struct Candidate {
   uint64_t w, den;
@@ -64,10 +24,7 @@ struct Candidate {
 static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::vector<mcmc::Float>& pi, float thr) {
   typedef unsigned __int128 u128;
   const uint64_t N = cfg.N, K = cfg.K;
-  // every training link once
-  std::vector<mcmc::Edge> links(cfg.training_edges.begin(), cfg.training_edges.end());
-  std::sort(links.begin(), links.end());
-  links.erase(std::unique(links.begin(), links.end()), links.end());
+  const std::vector<mcmc::Edge> links = SortedTrainingLinks(cfg);
   std::vector<std::vector<uint32_t>> in(N);
   std::vector<uint64_t> overlap(K * K, 0), directed(K * K, 0), want(K * K, 0);
   for (uint64_t a = 0; a < N; ++a) {
@@ -123,77 +80,38 @@ static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::ve
 }
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, graph));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  std::vector<mcmc::Float> pi;
-  for (uint64_t a = 0; a < N; ++a) {
-    const std::vector<mcmc::Float> row = learner.GetPiRow(static_cast<mcmc::Vertex>(a));
-    pi.insert(pi.end(), row.begin(), row.end());
-  }
+  Fitted fit(N, graph, device);
+  mcmc::Learner& learner = fit.learner;
+  const mcmc::Config& cfg = fit.cfg;
+  const std::vector<mcmc::Float> pi = fit.Pi();
   // an ordinary threshold, the start value's neighbourhood and one above every value (0 would be K^2 updates per link)
   for (float thr : {0.05f, 1.0f / 64, 2.0f}) Check(learner, cfg, pi, thr);
-  // the read-out does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
+  ExpectUnperturbed(fit);
   int threw = 0;
   mcmc::Learner::Linked r;
   std::vector<uint64_t> m;
   for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) {
-    try {
-      learner.LinkedCommunities(bad, 4, "density", 1, &r);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-    try {
-      learner.CommunityLinks(bad, &m);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
+    threw += Throws([&] { learner.LinkedCommunities(bad, 4, "density", 1, &r); });
+    threw += Throws([&] { learner.CommunityLinks(bad, &m); });
   }
   EXPECT(threw == 8);
-  for (uint32_t top : {0u, 65u}) {
-    try {
-      learner.LinkedCommunities(0.05f, top, "density", 1, &r);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
-  try {
-    learner.LinkedCommunities(0.05f, 4, "jaccard", 1, &r);
-  } catch (const std::invalid_argument&) {
-    ++threw;
-  }
+  for (uint32_t top : {0u, 65u}) threw += Throws([&] { learner.LinkedCommunities(0.05f, top, "density", 1, &r); });
+  threw += Throws([&] { learner.LinkedCommunities(0.05f, 4, "jaccard", 1, &r); });
   EXPECT(threw == 11);
   if (dir) {
     const std::string d(dir);
     // (the learner has moved on: the file and the checkpoint are of the same, current state)
     std::ofstream f(d + "/linked.txt");
-    EXPECT(learner.WriteLinkedCommunities(&f, 0.05f, 4, "density"));
-    std::ofstream lf(d + "/links.txt");  // the training links, for the reader of linked.txt
-    EXPECT(learner.WriteLinkCommunities(&lf, 1, 0) && lf.good());
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    EXPECT(f.good() && ck.good());
+    EXPECT(learner.WriteLinkedCommunities(&f, 0.05f, 4, "density") && f.good());
+    WriteTrainingLinks(learner, d);
+    WriteCheckpoint(learner, d);
   }
 }
 
 int main(int argc, char** argv) {
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   RunOnce(N, edges, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

@@ -11,19 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
+#include "postfit_test.h"
 
 struct RunResult {
   mcmc::Float p0, p1, p2;
@@ -193,8 +181,7 @@ static int CheckpointMode(const std::string& mode, const std::string& dir) {
     learner.Run(iters);
     WritePpx(dir + "/cpp_from_py_ppx.txt", learner.HeldoutPerplexity());
   }
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }
 
 int main(int argc, char** argv) {
@@ -228,6 +215,5 @@ int main(int argc, char** argv) {
   EXPECT(std::fabs(s - 1.0) < 1e-4);
   for (size_t k = 0; k + 1 < a.beta.size(); k += 2) EXPECT(std::fabs(a.beta[k] + a.beta[k + 1] - 1.0f) < 1e-6f);
   // error behaviour: phi.cc:732
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

@@ -8,52 +8,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <string>
 #include <vector>
 
 #include "ammsb_linkcomm.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
+#include "postfit_test.h"
 
 struct Model {
   uint64_t N, K;
@@ -61,25 +21,15 @@ struct Model {
   float eps;
 };
 
-static Model Fetch(mcmc::Learner& learner, const mcmc::Config& cfg) {
+static Model Fetch(Fitted& fit) {
   Model m;
-  m.N = cfg.N;
-  m.K = cfg.K;
-  m.eps = mcmc::MakeKernelParams(cfg).epsilon;
-  m.pi.resize(m.N * m.K);
-  for (uint64_t a = 0; a < m.N; ++a) {
-    const std::vector<mcmc::Float> row = learner.GetPiRow(static_cast<mcmc::Vertex>(a));
-    std::copy(row.begin(), row.end(), m.pi.begin() + a * m.K);
-  }
-  const std::vector<mcmc::Float> beta = learner.GetBeta();
+  m.N = fit.cfg.N;
+  m.K = fit.cfg.K;
+  m.eps = mcmc::MakeKernelParams(fit.cfg).epsilon;
+  m.pi = fit.Pi();
+  const std::vector<mcmc::Float> beta = fit.learner.GetBeta();
   for (uint64_t k = 0; k < m.K; ++k) m.beta.push_back(beta[2 * k + 1]);
   return m;
-}
-
-static uint32_t Bits(float x) {
-  uint32_t b;
-  memcpy(&b, &x, 4);
-  return b;
 }
 
 // -> mismatching edges; slot0[i] = the community in slot 0 (K: none, K + 1: an end out of range)
@@ -132,19 +82,10 @@ static uint64_t Check(mcmc::Learner& learner, const Model& m, const std::vector<
 }
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, graph));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  const Model m = Fetch(learner, cfg);
-  std::vector<mcmc::Edge> links(cfg.training_edges.begin(), cfg.training_edges.end());
-  std::sort(links.begin(), links.end());
-  links.erase(std::unique(links.begin(), links.end()), links.end());
+  Fitted fit(N, graph, device);
+  mcmc::Learner& learner = fit.learner;
+  const Model m = Fetch(fit);
+  const std::vector<mcmc::Edge> links = SortedTrainingLinks(fit.cfg);
   std::vector<mcmc::Edge> edges(links.begin(), links.begin() + std::min<size_t>(links.size(), 20000));
   for (size_t i = 0; i < 500; ++i) edges.push_back((edges[i] << 32) | (edges[i] >> 32));  // ends swapped
   edges.push_back((7ull << 32) | 7ull);                                                   // a == b
@@ -166,46 +107,30 @@ static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, bool devic
     printf("LinkCommunitySizes min_term=%g: %llu links, %llu unexplained\n", static_cast<double>(min_term),
            (unsigned long long)total, (unsigned long long)sizes[m.K]);
   }
-  // the read-out does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
+  ExpectUnperturbed(fit);
   int threw = 0;
   std::vector<uint32_t> ids;
   std::vector<mcmc::Float> terms, prob;
   std::vector<uint64_t> sizes;
-  for (int c = 0; c < 5; ++c) {
-    try {
-      if (c == 0) learner.LinkCommunities(edges, 0, 0, &ids, &terms, &prob);
-      if (c == 1) learner.LinkCommunities(edges, 17, 0, &ids, &terms, &prob);
-      if (c == 2) learner.LinkCommunities(edges, 1, -1e-9f, &ids, &terms, &prob);
-      if (c == 3) learner.LinkCommunities(edges, 1, NAN, &ids, &terms, &prob);
-      if (c == 4) learner.LinkCommunitySizes(INFINITY, &sizes);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
+  threw += Throws([&] { learner.LinkCommunities(edges, 0, 0, &ids, &terms, &prob); });
+  threw += Throws([&] { learner.LinkCommunities(edges, 17, 0, &ids, &terms, &prob); });
+  threw += Throws([&] { learner.LinkCommunities(edges, 1, -1e-9f, &ids, &terms, &prob); });
+  threw += Throws([&] { learner.LinkCommunities(edges, 1, NAN, &ids, &terms, &prob); });
+  threw += Throws([&] { learner.LinkCommunitySizes(INFINITY, &sizes); });
   EXPECT(threw == 5);
   if (dir) {
     const std::string d(dir);
     // (the learner has moved on since Fetch: the file and the checkpoint are of the same, current state)
     std::ofstream f(d + "/linkcomm.txt");
-    EXPECT(learner.WriteLinkCommunities(&f, 3, 0));
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    EXPECT(f.good() && ck.good());
+    EXPECT(learner.WriteLinkCommunities(&f, 3, 0) && f.good());
+    WriteCheckpoint(learner, d);
   }
 }
 
 int main(int argc, char** argv) {
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   RunOnce(N, edges, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

@@ -10,52 +10,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <string>
 #include <vector>
 
 #include "ammsb_linkpred.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
+#include "postfit_test.h"
 
 struct Model {
   uint64_t N, K;
@@ -73,17 +33,14 @@ struct Model {
   }
 };
 
-static Model Fetch(mcmc::Learner& learner, const mcmc::Config& cfg) {
+static Model Fetch(Fitted& fit) {
   Model m;
-  m.N = cfg.N;
-  m.K = cfg.K;
-  m.eps = static_cast<double>(mcmc::MakeKernelParams(cfg).epsilon);
-  m.pi.resize(m.N * m.K);
-  for (uint64_t a = 0; a < m.N; ++a) {
-    const std::vector<mcmc::Float> row = learner.GetPiRow(static_cast<mcmc::Vertex>(a));
-    for (uint64_t k = 0; k < m.K; ++k) m.pi[a * m.K + k] = row[k];
-  }
-  const std::vector<mcmc::Float> beta = learner.GetBeta();
+  m.N = fit.cfg.N;
+  m.K = fit.cfg.K;
+  m.eps = static_cast<double>(mcmc::MakeKernelParams(fit.cfg).epsilon);
+  const std::vector<mcmc::Float> pi = fit.Pi();
+  m.pi.assign(pi.begin(), pi.end());
+  const std::vector<mcmc::Float> beta = fit.learner.GetBeta();
   for (uint64_t k = 0; k < m.K; ++k) {
     m.w.push_back(static_cast<double>(beta[2 * k + 1]) - m.eps);
     m.aw.push_back(std::fabs(m.w.back()));
@@ -173,16 +130,10 @@ static void CheckTop(mcmc::Learner& learner, const mcmc::Config& cfg, const Mode
 }
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& edges, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, edges));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  const Model m = Fetch(learner, cfg);
+  Fitted fit(N, edges, device);
+  mcmc::Learner& learner = fit.learner;
+  const mcmc::Config& cfg = fit.cfg;
+  const Model m = Fetch(fit);
   CheckPairs(learner, cfg, m);
   std::vector<mcmc::Vertex> nodes;
   for (uint32_t i = 0; i < 150; ++i) nodes.push_back(static_cast<mcmc::Vertex>((i * 131u) % N));
@@ -191,45 +142,29 @@ static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& edges, bool devic
   CheckTop(learner, cfg, m, nodes, 10, all);
   CheckTop(learner, cfg, m, nodes, 64, mcmc::Learner::kExcludeTraining);
   CheckTop(learner, cfg, m, std::vector<mcmc::Vertex>(nodes.begin(), nodes.begin() + 7), 1, 0);
-  // predicting does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
+  ExpectUnperturbed(fit);
   int threw = 0;
   std::vector<mcmc::Vertex> ids;
   std::vector<mcmc::Float> scores;
-  for (int c = 0; c < 4; ++c) {
-    try {
-      if (c == 0) learner.PredictLinks(nodes, 0, all, &ids, &scores);
-      if (c == 1) learner.PredictLinks(nodes, 65, all, &ids, &scores);
-      if (c == 2) learner.PredictLinks(nodes, 10, 4, &ids, &scores);
-      if (c == 3) learner.PredictLinks({static_cast<mcmc::Vertex>(N)}, 10, all, &ids, &scores);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
+  threw += Throws([&] { learner.PredictLinks(nodes, 0, all, &ids, &scores); });
+  threw += Throws([&] { learner.PredictLinks(nodes, 65, all, &ids, &scores); });
+  threw += Throws([&] { learner.PredictLinks(nodes, 10, 4, &ids, &scores); });
+  threw += Throws([&] { learner.PredictLinks({static_cast<mcmc::Vertex>(N)}, 10, all, &ids, &scores); });
   EXPECT(threw == 4);
   if (dir) {
     const std::string d(dir);
     // (the learner has moved on since Fetch: the file and the checkpoint are of the same, current state)
     std::vector<mcmc::Vertex> q(nodes.begin(), nodes.begin() + 151);
     std::ofstream f(d + "/links.txt");
-    EXPECT(learner.WritePredictedLinks(&f, q, 10, all));
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    EXPECT(f.good() && ck.good());
+    EXPECT(learner.WritePredictedLinks(&f, q, 10, all) && f.good());
+    WriteCheckpoint(learner, d);
   }
 }
 
 int main(int argc, char** argv) {
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   RunOnce(N, edges, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

@@ -9,59 +9,15 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iterator>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "ammsb_modularity.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
+#include "postfit_test.h"
 typedef unsigned __int128 u128;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
-
-static bool SameBits(const std::vector<double>& x, const std::vector<double>& y) {
-  return x.size() == y.size() && (x.empty() || memcmp(x.data(), y.data(), x.size() * sizeof(double)) == 0);
-}
 
 // the statement over a list of keys -> a score whose Derive() has run
 static mcmc::Learner::ModularityScore Statement(const std::vector<mcmc::Float>& pi, uint64_t N, uint64_t K, float thr,
@@ -105,10 +61,7 @@ static void Compare(const mcmc::Learner::ModularityScore& got, const mcmc::Learn
 
 static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::vector<mcmc::Float>& pi, float thr) {
   const uint64_t N = cfg.N, K = cfg.K;
-  // every training link once
-  std::vector<mcmc::Edge> links(cfg.training_edges.begin(), cfg.training_edges.end());
-  std::sort(links.begin(), links.end());
-  links.erase(std::unique(links.begin(), links.end()), links.end());
+  const std::vector<mcmc::Edge> links = SortedTrainingLinks(cfg);
   mcmc::Learner::ModularityScore got;
   learner.Modularity(thr, nullptr, &got);
   const mcmc::Learner::ModularityScore want = Statement(pi, N, K, thr, links);
@@ -128,49 +81,24 @@ static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::ve
 }
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, graph));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  std::vector<mcmc::Float> pi;
-  for (uint64_t a = 0; a < N; ++a) {
-    const std::vector<mcmc::Float> row = learner.GetPiRow(static_cast<mcmc::Vertex>(a));
-    pi.insert(pi.end(), row.begin(), row.end());
-  }
+  Fitted fit(N, graph, device);
+  mcmc::Learner& learner = fit.learner;
+  const mcmc::Config& cfg = fit.cfg;
+  const std::vector<mcmc::Float> pi = fit.Pi();
   // an ordinary threshold, the start value's neighbourhood, every stored number (O = K everywhere) and one above every value
   for (float thr : {0.05f, 1.0f / 64, 0.0f, 2.0f}) Check(learner, cfg, pi, thr);
-  // the read-out does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
+  ExpectUnperturbed(fit);
   int threw = 0;
   mcmc::Learner::ModularityScore r;
-  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) {
-    try {
-      learner.Modularity(bad, nullptr, &r);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
+  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) threw += Throws([&] { learner.Modularity(bad, nullptr, &r); });
   EXPECT(threw == 4);
   if (dir) {
     const std::string d(dir);
     // (the learner has moved on: the file and the checkpoint are of the same, current state)
     std::ofstream f(d + "/modularity.txt");
-    EXPECT(learner.WriteModularity(&f, 0.05f));
-    std::ofstream lf(d + "/links.txt");  // the training links, for the reader of modularity.txt
-    EXPECT(learner.WriteLinkCommunities(&lf, 1, 0) && lf.good());
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    EXPECT(f.good() && ck.good());
+    EXPECT(learner.WriteModularity(&f, 0.05f) && f.good());
+    WriteTrainingLinks(learner, d);
+    WriteCheckpoint(learner, d);
   }
 }
 
@@ -187,10 +115,8 @@ int main(int argc, char** argv) {
   EXPECT(hand.q == -1.0 && hand.q_each[0] == -1.0);
 
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   RunOnce(N, edges, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

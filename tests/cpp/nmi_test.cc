@@ -11,53 +11,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <limits>
 #include <string>
 #include <vector>
 
 #include "ammsb_nmi.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
+#include "postfit_test.h"
 
 static const double kInf = std::numeric_limits<double>::infinity();
 static const double kTol = std::ldexp(1.0, -47);
@@ -66,10 +26,6 @@ static double H1(int64_t x, double n) {
   if (x == 0) return 0.0;
   const double p = static_cast<double>(x) / n;
   return -(p * std::log2(p));
-}
-
-static bool SameBits(const std::vector<double>& a, const std::vector<double>& b) {
-  return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(double)));
 }
 
 static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::vector<mcmc::Float>& pi,
@@ -145,20 +101,10 @@ static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::ve
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, const std::vector<uint64_t>& offsets,
                     const std::vector<uint32_t>& members, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, graph));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  std::vector<mcmc::Float> pi;
-  for (uint64_t a = 0; a < N; ++a) {
-    const std::vector<mcmc::Float> row = learner.GetPiRow(static_cast<mcmc::Vertex>(a));
-    pi.insert(pi.end(), row.begin(), row.end());
-  }
+  Fitted fit(N, graph, device);
+  mcmc::Learner& learner = fit.learner;
+  const mcmc::Config& cfg = fit.cfg;
+  const std::vector<mcmc::Float> pi = fit.Pi();
   // an ordinary threshold, 0 (every d_k = N: H(Y_k) = 0), the start value's neighbourhood and one above every value
   for (float thr : {0.05f, 0.0f, 1.0f / 64, 2.0f}) Check(learner, cfg, pi, offsets, members, thr);
   mcmc::Learner::CoverNmi r;
@@ -171,76 +117,36 @@ static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, const std:
   EXPECT(r.H_truth.empty() && r.nmi_lfk == -1.0 && r.H_detected.size() == cfg.K);
   learner.CoverNMI({0, 0, 0}, {}, 0.05f, &r);
   EXPECT(r.H_truth == std::vector<double>(2, 0.0) && r.h_truth == std::vector<double>(2, 0.0) && r.nmi_lfk == -1.0);
-  // the comparison does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
+  ExpectUnperturbed(fit);
   int threw = 0;
-  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) {
-    try {
-      learner.CoverNMI(offsets, members, bad, &r);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
+  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) threw += Throws([&] { learner.CoverNMI(offsets, members, bad, &r); });
   EXPECT(threw == 4);
   const std::vector<std::vector<uint64_t>> bad_offsets = {{}, {1, 2}, {0, 3, 2, static_cast<uint64_t>(members.size())}, {0, 5}};
-  for (const auto& bad : bad_offsets) {
-    try {
-      learner.CoverNMI(bad, members, 0.05f, &r);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
+  for (const auto& bad : bad_offsets) threw += Throws([&] { learner.CoverNMI(bad, members, 0.05f, &r); });
   EXPECT(threw == 8);
   // NMI is defined on sets: a node twice inside one community is refused (twice in two communities is a cover)
   std::vector<uint32_t> twice = members;
   twice[offsets[7] + 3] = twice[offsets[7] + 2];
-  try {
-    learner.CoverNMI(offsets, twice, 0.05f, &r);
-  } catch (const std::invalid_argument&) {
-    ++threw;
-  }
+  threw += Throws([&] { learner.CoverNMI(offsets, twice, 0.05f, &r); });
   EXPECT(threw == 9);
   if (dir) {
     const std::string d(dir);
     // (the learner has moved on: the file and the checkpoint are of the same, current state)
     std::ofstream f(d + "/nmi.txt");
-    EXPECT(learner.WriteCoverNMI(&f, offsets, members, 0.05f));
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    std::ofstream tf(d + "/truth.txt");
-    for (size_t g = 0; g + 1 < offsets.size(); ++g) {
-      tf << offsets[g + 1] - offsets[g];
-      for (uint64_t i = offsets[g]; i < offsets[g + 1]; ++i) tf << " " << members[i];
-      tf << "\n";
-    }
-    EXPECT(f.good() && ck.good() && tf.good());
+    EXPECT(learner.WriteCoverNMI(&f, offsets, members, 0.05f) && f.good());
+    WriteCheckpoint(learner, d);
+    WriteTruth(d, offsets, members);
   }
 }
 
 int main(int argc, char** argv) {
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
-  std::vector<std::vector<mcmc::Vertex>> cover = mcmc::GenerateSyntheticCover(N, 16, 7);
-  EXPECT(cover.size() == 16);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   // a member == N, a member == 2^32 - 1, an empty community and a small one; no node twice inside a community
-  cover[2][1] = static_cast<mcmc::Vertex>(N);
-  cover[5].back() = 0xFFFFFFFFu;
-  cover.insert(cover.begin() + 9, std::vector<mcmc::Vertex>());
-  cover.push_back({3, 1, 4});
-  std::vector<uint64_t> offsets(1, 0);
+  std::vector<uint64_t> offsets;
   std::vector<uint32_t> members;
-  for (const auto& c : cover) {
-    members.insert(members.end(), c.begin(), c.end());
-    offsets.push_back(members.size());
-  }
+  SpoiltCover(PlantedCover(N), N, &offsets, &members);
   RunOnce(N, edges, offsets, members, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, offsets, members, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

@@ -8,60 +8,19 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <fstream>
 #include <string>
 #include <vector>
 
 #include "ammsb_quality.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
+#include "postfit_test.h"
 
-namespace clcuda = mcmc::clcuda;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
-
-static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::vector<mcmc::Edge>& links, float thr) {
-  const uint64_t N = cfg.N, K = cfg.K;
+static void Check(Fitted& fit, const std::vector<mcmc::Edge>& links, float thr) {
+  const uint64_t N = fit.cfg.N, K = fit.cfg.K;
   std::vector<char> member(N * K);
   std::vector<uint64_t> want_size(K, 0), want_in(K, 0), want_out(K, 0);
-  for (uint64_t a = 0; a < N; ++a) {
-    const std::vector<mcmc::Float> row = learner.GetPiRow(static_cast<mcmc::Vertex>(a));
-    for (uint64_t k = 0; k < K; ++k) want_size[k] += (member[a * K + k] = row[k] >= thr);
-  }
+  const std::vector<mcmc::Float> pi = fit.Pi();  // (fetched for every threshold)
+  for (uint64_t i = 0; i < N * K; ++i) want_size[i % K] += (member[i] = pi[i] >= thr);
   uint64_t want_uncovered = 0;
   for (mcmc::Edge e : links) {
     const uint64_t a = e >> 32, b = e & 0xFFFFFFFFull;
@@ -76,7 +35,7 @@ static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::ve
   }
   std::vector<uint64_t> size, internal, boundary;
   uint64_t uncovered = ~0ull;
-  learner.CommunityQuality(thr, &size, &internal, &boundary, &uncovered);
+  fit.learner.CommunityQuality(thr, &size, &internal, &boundary, &uncovered);
   EXPECT(size == want_size);
   EXPECT(internal == want_in);
   EXPECT(boundary == want_out);
@@ -88,61 +47,37 @@ static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::ve
 }
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, graph));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  std::vector<mcmc::Edge> links(cfg.training_edges.begin(), cfg.training_edges.end());
-  std::sort(links.begin(), links.end());
-  links.erase(std::unique(links.begin(), links.end()), links.end());
+  Fitted fit(N, graph, device);
+  mcmc::Learner& learner = fit.learner;
+  const mcmc::Config& cfg = fit.cfg;
+  const std::vector<mcmc::Edge> links = SortedTrainingLinks(cfg);
   // an ordinary threshold, 0 (everybody is a member of everything) and one above every value (all links uncovered)
-  for (float thr : {0.05f, 0.0f, 1.0f / 64, 2.0f}) Check(learner, cfg, links, thr);
+  for (float thr : {0.05f, 0.0f, 1.0f / 64, 2.0f}) Check(fit, links, thr);
   std::vector<uint64_t> size, internal, boundary;
   uint64_t uncovered = 0;
   learner.CommunityQuality(0.0f, &size, &internal, &boundary, &uncovered);
   EXPECT(uncovered == 0 && internal == std::vector<uint64_t>(cfg.K, links.size()) && size == std::vector<uint64_t>(cfg.K, N));
   learner.CommunityQuality(2.0f, &size, &internal, &boundary, &uncovered);
   EXPECT(uncovered == links.size() && boundary == std::vector<uint64_t>(cfg.K, 0));
-  // the read-out does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
+  ExpectUnperturbed(fit);
   int threw = 0;
-  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) {
-    try {
-      learner.CommunityQuality(bad, &size, &internal, &boundary, &uncovered);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
+  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY})
+    threw += Throws([&] { learner.CommunityQuality(bad, &size, &internal, &boundary, &uncovered); });
   EXPECT(threw == 4);
   if (dir) {
     const std::string d(dir);
     // (the learner has moved on: the file and the checkpoint are of the same, current state)
     std::ofstream f(d + "/quality.txt");
-    EXPECT(learner.WriteCommunityQuality(&f, 0.05f));
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    std::ofstream lf(d + "/links.txt");
-    EXPECT(learner.WriteLinkCommunities(&lf, 1, 0));
-    EXPECT(f.good() && ck.good() && lf.good());
+    EXPECT(learner.WriteCommunityQuality(&f, 0.05f) && f.good());
+    WriteCheckpoint(learner, d);
+    WriteTrainingLinks(learner, d);
   }
 }
 
 int main(int argc, char** argv) {
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   RunOnce(N, edges, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

@@ -5,60 +5,13 @@
 //                        sizes) and DIR/communities.txt of the first run, for a bit-level check from the other host.
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <numeric>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "ammsb_readout.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
-
-static uint32_t Bits(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  return u;
-}
+#include "postfit_test.h"
 
 static void Check(mcmc::Learner& learner, uint64_t N, uint32_t K, uint32_t top, float thr) {
   std::vector<uint32_t> ids, count;
@@ -115,33 +68,14 @@ static void Put(std::ofstream& f, const std::vector<T>& v) {
 }
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& edges, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, edges));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  const uint32_t K = static_cast<uint32_t>(cfg.K);
+  Fitted fit(N, edges, device);
+  mcmc::Learner& learner = fit.learner;
+  const uint32_t K = static_cast<uint32_t>(fit.cfg.K);
   Check(learner, N, K, 4, 0.0f);
   Check(learner, N, K, 16, 0.02f);
   Check(learner, N, K, 1, 0.5f);
-  // reading out does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
-  bool threw = false;
-  try {
-    learner.Memberships(17, 0.0f, nullptr, nullptr, nullptr, nullptr);
-  } catch (const std::invalid_argument&) {
-    threw = true;
-  }
-  EXPECT(threw);
+  ExpectUnperturbed(fit);
+  EXPECT(Throws([&] { learner.Memberships(17, 0.0f, nullptr, nullptr, nullptr, nullptr); }));
   if (dir) {
     const std::string d(dir);
     const uint32_t top = 4;
@@ -160,18 +94,15 @@ static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& edges, bool devic
     Put(f, sizes);
     std::ofstream c(d + "/communities.txt");
     EXPECT(learner.WriteCommunities(&c, top, thr));
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    EXPECT(f.good() && c.good() && ck.good());
+    EXPECT(f.good() && c.good());
+    WriteCheckpoint(learner, d);
   }
 }
 
 int main(int argc, char** argv) {
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   RunOnce(N, edges, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

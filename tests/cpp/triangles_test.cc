@@ -9,58 +9,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <string>
 #include <vector>
 
 #include "ammsb_triangles.h"
-#include "mcmc/data.h"
-#include "mcmc/learner.h"
-
-namespace clcuda = mcmc::clcuda;
+#include "postfit_test.h"
 typedef mcmc::Learner::TrianglesResult Result;
-
-static int fails = 0;
-#define EXPECT(cond)                                          \
-  do {                                                        \
-    if (!(cond)) {                                            \
-      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond);   \
-      ++fails;                                                \
-    }                                                         \
-  } while (0)
-
-static bool Prepare(mcmc::Config* cfg, uint64_t N, std::vector<mcmc::Edge> e) {
-  cfg->N = N;
-  cfg->K = 64;
-  cfg->mini_batch_size = 256;
-  cfg->num_node_sample = 16;
-  cfg->heldout_ratio = 0.05;
-  cfg->alpha = static_cast<mcmc::Float>(1) / cfg->K;
-  cfg->phi_wg_size = cfg->beta_wg_size = cfg->ppx_wg_size = 64;
-  cfg->beta_seed = {44, 45};
-  cfg->neighbor_seed = {56, 57};
-  srand(12345);
-  bool ok = false;
-  for (int attempt = 0; attempt < 64 && !ok; ++attempt) {
-    cfg->training_edges.clear();
-    cfg->heldout_edges.clear();
-    ok = mcmc::GenerateSetsFromEdges(cfg->N, e, cfg->heldout_ratio, &cfg->training_edges, &cfg->heldout_edges,
-                                     &cfg->training, &cfg->heldout);
-    if (!ok) e.resize(e.size() - 40);
-  }
-  if (!ok) return false;
-  cfg->trainingGraph.reset(new mcmc::Graph(cfg->N, cfg->training_edges));
-  cfg->heldoutGraph.reset(new mcmc::Graph(cfg->N, cfg->heldout_edges));
-  cfg->E = e.size();
-  return true;
-}
-
-template <class T>
-static bool SameBits(const std::vector<T>& x, const std::vector<T>& y) {
-  return x.size() == y.size() && (x.empty() || memcmp(x.data(), y.data(), x.size() * sizeof(T)) == 0);
-}
 
 // the statement over a list of keys -> a result whose Derive() has run
 static Result Statement(const std::vector<mcmc::Float>& pi, uint64_t N, uint64_t K, float thr, const std::vector<mcmc::Edge>& keys) {
@@ -165,50 +121,25 @@ static void Check(mcmc::Learner& learner, const mcmc::Config& cfg, const std::ve
 }
 
 static void RunOnce(uint64_t N, const std::vector<mcmc::Edge>& graph, bool device, const char* dir) {
-  mcmc::Config cfg;
-  cfg.device_sampling = cfg.async_launch = cfg.graph_launch = device;
-  EXPECT(Prepare(&cfg, N, graph));
-  clcuda::Platform platform((size_t)0);
-  clcuda::Device dev(platform, 0);
-  clcuda::Context context(dev);
-  clcuda::Queue queue(context, dev);
-  mcmc::Learner learner(cfg, queue);
-  learner.Run(30);
-  std::vector<mcmc::Float> pi;
-  for (uint64_t a = 0; a < N; ++a) {
-    const std::vector<mcmc::Float> row = learner.GetPiRow(static_cast<mcmc::Vertex>(a));
-    pi.insert(pi.end(), row.begin(), row.end());
-  }
+  Fitted fit(N, graph, device);
+  mcmc::Learner& learner = fit.learner;
+  const mcmc::Config& cfg = fit.cfg;
+  const std::vector<mcmc::Float> pi = fit.Pi();
   Check(learner, cfg, pi, 0.05f);
   Check(learner, cfg, pi, 1.0f / 64);
   Check(learner, cfg, pi, 0.0f);
-  // the read-out does not perturb the run: the state after 30 more steps equals that of an undisturbed learner
-  mcmc::Learner plain(cfg, queue);
-  plain.Run(30);
-  plain.Run(30);
-  learner.Run(30);
-  EXPECT(learner.HeldoutPerplexity() == plain.HeldoutPerplexity());
-  EXPECT(learner.GetBeta() == plain.GetBeta() && learner.GetPiRow(17) == plain.GetPiRow(17));
+  ExpectUnperturbed(fit);
   int threw = 0;
   Result r;
-  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) {
-    try {
-      learner.Triangles(bad, nullptr, &r);
-    } catch (const std::invalid_argument&) {
-      ++threw;
-    }
-  }
+  for (float bad : {-1e-9f, -1.0f, NAN, INFINITY}) threw += Throws([&] { learner.Triangles(bad, nullptr, &r); });
   EXPECT(threw == 4);
   if (dir) {
     const std::string d(dir);
     // (the learner has moved on: the file and the checkpoint are of the same, current state)
     std::ofstream f(d + "/triangles.txt");
-    EXPECT(learner.WriteTriangles(&f, 0.05f));
-    std::ofstream lf(d + "/links.txt");  // the training links, for the reader of triangles.txt
-    EXPECT(learner.WriteLinkCommunities(&lf, 1, 0) && lf.good());
-    std::ofstream ck(d + "/cpp.ckpt", std::ios::binary);
-    EXPECT(learner.Serialize(&ck));
-    EXPECT(f.good() && ck.good());
+    EXPECT(learner.WriteTriangles(&f, 0.05f) && f.good());
+    WriteTrainingLinks(learner, d);
+    WriteCheckpoint(learner, d);
   }
 }
 
@@ -238,10 +169,8 @@ int main(int argc, char** argv) {
   EXPECT(threw == 1);
 
   const uint64_t N = 20000;
-  const std::vector<mcmc::Edge> edges = mcmc::GenerateSyntheticGraph(N, 16, 16, 7);
-  EXPECT(edges.size() > 100000);
+  const std::vector<mcmc::Edge> edges = TestGraph(N);
   RunOnce(N, edges, false, argc > 1 ? argv[1] : nullptr);
   RunOnce(N, edges, true, nullptr);
-  printf(fails ? "FAILED (%d)\n" : "OK\n", fails);
-  return fails ? 1 : 0;
+  return Finish();
 }

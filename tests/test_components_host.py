@@ -214,3 +214,19 @@ def test_the_library_is_built_by_build_and_exports_what_its_header_declares(cc):
     assert hasattr(ops, "CommunityComponents")
     src = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "csrc", "ammsb_components.hip")).read()
     assert set(re.findall(r"__global__ [^\n]*void (components_[a-z0-9_]+)\(", src)) == set(cc.KERNEL_FORMS)
+
+
+def test_the_shared_test_header_rebuilds_every_post_fit_test_and_nothing_else(cc):
+    """tests/cpp/postfit_test.h is a prerequisite of the C++ tests: in a built tree (the fixture's build()), a change to it
+    compiles every <analysis>_test of the Makefile's POSTFIT list again, from its own source, and leaves the library"""
+    import make_dry_run as dry
+    makefile = open(os.path.join(ROOT, "mcmc-ammsb-gpu_amd", "host", "Makefile")).read()
+    postfit = re.search(r"^POSTFIT\s*=\s*(.+)$", makefile, re.M).group(1).split()
+    assert len(postfit) >= 13 and "components" in postfit and "readout" in postfit
+    fresh = dry.commands("host", "all", remake_all=False)
+    after = dry.commands("host", "all", remake_all=False, touched=("../../tests/cpp/postfit_test.h",))
+    for name in postfit:
+        out, src = "../%s_test" % name, "tests/cpp/%s_test.cc" % name
+        assert not dry.builds(fresh, out) and dry.builds(after, out, src), name
+        assert '#include "postfit_test.h"' in open(os.path.join(ROOT, src)).read(), name
+    assert not dry.builds(after, "../libammsb_host.so") and not dry.builds(after, "../ammsb_main")
