@@ -299,6 +299,33 @@ class Learner {
   // nslots k0 root0 size0 ...` per node: integers throughout.
   bool WriteCommunityComponents(std::ostream* out, Float threshold, const std::vector<Edge>* edges = nullptr);
 
+  // Where does a node sit inside a community?  The k-core decomposition of the subgraph every community of the cover pi[a,
+  // k] >= threshold induces in the simple adjacency of `edges` (as Triangles builds it on the host, without its limit on a
+  // row's length; nullptr: every training link once), the integers of include/ammsb_cores.h: per community members,
+  // inlinks2, degeneracy, nucleus, isolated; the memberships as a CSR over the nodes, offsets [N + 1] and per slot
+  // community, indeg, core; best_core, best_comm (-1: no community), in_nucleus per node; L, skipped, dropped, all exact,
+  // and the launch counts scans and rounds (diagnostic).  Derive() is the header's float64 statement over them.
+  // std::invalid_argument on a bad threshold, on a cover of 2^32 memberships or more and on neighbour lists of 2^32
+  // entries or more than max_bytes (both messages name the threshold).  Waits, reads and perturbs like CommunityQuality.
+  struct CoresResult {
+    std::vector<uint64_t> members, inlinks2, nucleus, isolated;  // [K]
+    std::vector<uint32_t> degeneracy;                             // [K]
+    std::vector<uint64_t> offsets;                                // [N + 1]
+    std::vector<uint16_t> community;                              // [M]
+    std::vector<uint32_t> indeg, core;                            // [M]
+    std::vector<uint32_t> best_core, in_nucleus;                  // [N]
+    std::vector<int32_t> best_comm;                               // [N]
+    uint64_t L = 0, skipped = 0, dropped = 0, scans = 0, rounds = 0;
+    std::vector<double> coreness;                                 // [M], -1 where the degeneracy is 0
+    std::vector<double> nucleus_share, mean_core;                 // [K], -1 where members is 0
+    void Derive();
+  };
+  void CommunityCores(Float threshold, CoresResult* result, const std::vector<Edge>* edges = nullptr,
+                      uint64_t max_bytes = 4ull << 30);
+  // `# N K M L threshold skipped dropped`, `c k members inlinks2 degeneracy nucleus isolated` per community, `n a nslots k0
+  // indeg0 core0 ...` per node: integers throughout.
+  bool WriteCommunityCores(std::ostream* out, Float threshold, const std::vector<Edge>* edges = nullptr);
+
  private:
   Float DoSample(Sample* sample);        // learner.cc:175-194
   Float DoSampleDevice(Sample* sample);  // Config::device_sampling: csrc/ammsb_minibatch.hip instead of sample.cc

@@ -19,6 +19,7 @@
 #include "ammsb_roles.h"
 #include "ammsb_triangles.h"
 #include "ammsb_components.h"
+#include "ammsb_cores.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1184,6 +1185,36 @@ void Learner::TrianglesResult::Derive() {
   avg_clustering = some ? sum_local / static_cast<double>(some) : -1.0;
 }
 
+// The simple adjacency of a key list, which Triangles and CommunityCores share: both directions of every key with both ends
+// < N, each row sorted and made unique, loops left out.  *valid: the keys with both ends < N; *lost: those with an end >= N.
+// max_row > 0: std::invalid_argument(too_long) on a longer row.
+static void SimpleAdjacency(const std::vector<Edge>& list, uint64_t N, uint64_t max_row, const char* too_long,
+                            std::vector<uint64_t>* offsets, std::vector<Vertex>* targets, uint64_t* valid, uint64_t* lost) {
+  std::vector<std::vector<Vertex>> rows(N);
+  *valid = *lost = 0;
+  for (Edge e : list) {
+    const uint64_t a = e >> 32, b = e & 0xFFFFFFFFull;
+    if (a >= N || b >= N) {
+      ++*lost;
+      continue;
+    }
+    ++*valid;
+    if (a == b) continue;
+    rows[a].push_back(static_cast<Vertex>(b));
+    rows[b].push_back(static_cast<Vertex>(a));
+  }
+  offsets->assign(N + 1, 0);
+  targets->clear();
+  for (uint64_t a = 0; a < N; ++a) {
+    std::sort(rows[a].begin(), rows[a].end());
+    rows[a].erase(std::unique(rows[a].begin(), rows[a].end()), rows[a].end());
+    if (max_row && rows[a].size() > max_row) throw std::invalid_argument(too_long);
+    targets->insert(targets->end(), rows[a].begin(), rows[a].end());
+    (*offsets)[a + 1] = targets->size();
+    std::vector<Vertex>().swap(rows[a]);
+  }
+}
+
 void Learner::Triangles(Float threshold, const std::vector<Edge>* edges, TrianglesResult* result) {
   CheckThreshold("Triangles", threshold);
   DrainAsync();
@@ -1193,29 +1224,10 @@ void Learner::Triangles(Float threshold, const std::vector<Edge>* edges, Triangl
   // the simple adjacency: both directions of every valid key, each row sorted and made unique, loops left out
   std::vector<Edge> training;
   const std::vector<Edge>& list = *EdgesOrTraining("Triangles", edges, cfg_, &training);
-  std::vector<std::vector<Vertex>> rows(N);
-  uint64_t valid = 0, lost = 0;  // keys with both ends < N; with an end >= N
-  for (Edge e : list) {
-    const uint64_t a = e >> 32, b = e & 0xFFFFFFFFull;
-    if (a >= N || b >= N) {
-      ++lost;
-      continue;
-    }
-    ++valid;
-    if (a == b) continue;
-    rows[a].push_back(static_cast<Vertex>(b));
-    rows[b].push_back(static_cast<Vertex>(a));
-  }
-  std::vector<uint64_t> offsets(N + 1, 0);
+  std::vector<uint64_t> offsets;
   std::vector<Vertex> targets;
-  for (uint64_t a = 0; a < N; ++a) {
-    std::sort(rows[a].begin(), rows[a].end());
-    rows[a].erase(std::unique(rows[a].begin(), rows[a].end()), rows[a].end());
-    if (rows[a].size() > AMMSB_TRIANGLES_MAX_ROW) throw std::invalid_argument("Triangles: a row of more than 65535 targets");
-    targets.insert(targets.end(), rows[a].begin(), rows[a].end());
-    offsets[a + 1] = targets.size();
-    std::vector<Vertex>().swap(rows[a]);
-  }
+  uint64_t valid = 0, lost = 0;  // keys with both ends < N; with an end >= N
+  SimpleAdjacency(list, N, AMMSB_TRIANGLES_MAX_ROW, "Triangles: a row of more than 65535 targets", &offsets, &targets, &valid, &lost);
   TrianglesResult& r = *result;
   r.M = targets.size();
   r.skipped = lost;
@@ -1399,6 +1411,194 @@ bool Learner::WriteCommunityComponents(std::ostream* out, Float threshold, const
   for (size_t a = 0; a + 1 < r.offsets.size(); ++a) {
     *out << "n " << a << " " << r.offsets[a + 1] - r.offsets[a];
     for (uint64_t s = r.offsets[a]; s < r.offsets[a + 1]; ++s) *out << " " << r.community[s] << " " << r.root[s] << " " << r.size[s];
+    *out << "\n";
+  }
+  return static_cast<bool>(*out);
+}
+
+// ---- where does a node sit inside a community: libammsb_cores.so over libammsb_connect.so's mask of pi, the slot numbering
+// of libammsb_components.so and one simple CSR adjacency
+void Learner::CoresResult::Derive() {
+#pragma STDC FP_CONTRACT OFF
+  const size_t K = members.size(), M = core.size();
+  // (every integer is converted once, to nearest even)
+  coreness.assign(M, -1.0);
+  std::vector<uint64_t> total(K, 0);
+  for (size_t s = 0; s < M; ++s) {
+    const uint32_t top = degeneracy[community[s]];
+    total[community[s]] += core[s];
+    if (top > 0) coreness[s] = static_cast<double>(core[s]) / static_cast<double>(top);
+  }
+  nucleus_share.assign(K, -1.0);
+  mean_core.assign(K, -1.0);
+  for (size_t k = 0; k < K; ++k) {
+    if (members[k] == 0) continue;
+    nucleus_share[k] = static_cast<double>(nucleus[k]) / static_cast<double>(members[k]);
+    mean_core[k] = static_cast<double>(total[k]) / static_cast<double>(members[k]);
+  }
+}
+
+void Learner::CommunityCores(Float threshold, CoresResult* result, const std::vector<Edge>* edges, uint64_t max_bytes) {
+  CheckThreshold("CommunityCores", threshold);
+  DrainAsync();
+  queue_.Finish();
+  const uint64_t N = pi_->Rows(), K = pi_->Cols();
+  if (K == 0 || K > AMMSB_CORES_MAX_COLS) throw std::runtime_error("CommunityCores: K outside 1..8192");
+  std::vector<Edge> training;
+  const std::vector<Edge>& list = *EdgesOrTraining("CommunityCores", edges, cfg_, &training);
+  std::vector<uint64_t> offsets;
+  std::vector<Vertex> targets;
+  uint64_t valid = 0, lost = 0;
+  SimpleAdjacency(list, N, 0, "", &offsets, &targets, &valid, &lost);
+  CoresResult& r = *result;
+  r = CoresResult();
+  r.skipped = lost;
+  r.dropped = valid - targets.size() / 2;
+  r.members.assign(K, 0);
+  r.inlinks2.assign(K, 0);
+  r.nucleus.assign(K, 0);
+  r.isolated.assign(K, 0);
+  r.degeneracy.assign(K, 0);
+  r.offsets.assign(N + 1, 0);
+  r.best_core.assign(N, 0);
+  r.in_nucleus.assign(N, 0);
+  r.best_comm.assign(N, -1);
+  if (N > 0) {
+    const uint32_t cols = static_cast<uint32_t>(K);
+    hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
+    const clcuda::Context context = queue_.GetContext();
+    if (targets.empty()) targets.push_back(0);  // (a buffer needs a byte; no offset reaches it)
+    clcuda::Buffer<uint32_t> d_node4(context, 4 * N);  // own best_core best_comm in_nucleus
+    uint32_t* const d_node = d_node4();
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    int rc = ammsb_components_own(d_mask(), N, cols, d_node, stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_components_own", rc, ammsb_components_last_error());
+    std::vector<uint32_t> own(N);
+    d_node4.Read(queue_, N, own.data());
+    queue_.Finish();
+    for (uint64_t a = 0; a < N; ++a) r.offsets[a + 1] = r.offsets[a] + own[a];
+    const uint64_t M = r.offsets[N];
+    if (M >= AMMSB_CORES_MAX_SLOTS)
+      throw std::invalid_argument("CommunityCores: the cover has " + std::to_string(M) + " memberships at the threshold " +
+                                  G9(threshold) + "; the library takes fewer than 2^32 (raise the threshold)");
+    const uint64_t m1 = std::max<uint64_t>(M, 1);  // (a buffer needs a byte)
+    clcuda::Buffer<uint64_t> d_base(context, queue_, r.offsets.begin(), r.offsets.end());
+    clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
+    clcuda::Buffer<Vertex> d_targets(context, queue_, targets.begin(), targets.end());
+    clcuda::Buffer<uint64_t> d_sums(context, 4 * K + 6);  // members inlinks2 nucleus isolated; counts; tail, next_level
+    clcuda::Buffer<uint32_t> d_slot(context, 3 * m1), d_top(context, K);  // slot_node / queue, parent / deg, indeg; degeneracy
+    clcuda::Buffer<uint16_t> d_comm(context, m1);
+    Zero("CommunityCores", d_sums(), (4 * K + 6) * sizeof(uint64_t), stream);
+    Zero("CommunityCores", d_top(), K * sizeof(uint32_t), stream);
+    uint64_t* const counts = d_sums() + 4 * K;
+    uint64_t* const tail_p = counts + 4;
+    uint32_t* const next_p = reinterpret_cast<uint32_t*>(counts + 5);
+    uint32_t* const queue = d_slot();      // (slot_node and parent are only there for ammsb_components_slots to write)
+    uint32_t* const deg = d_slot() + m1;
+    uint32_t* const indeg = d_slot() + 2 * m1;
+    std::vector<uint32_t> h_indeg(m1, 0);
+    if (M > 0) {
+      rc = ammsb_components_slots(d_mask(), N, cols, d_base(), M, 0, N, queue, d_comm(), deg, stream);
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_components_slots", rc, ammsb_components_last_error());
+      rc = ammsb_cores_degrees(d_mask(), N, cols, d_base(), M, d_offsets(), d_targets(), 0, N, indeg, counts, stream);
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_cores_degrees", rc, ammsb_cores_last_error());
+      // nbr_off: a host prefix sum over the downloaded indeg
+      if (hipMemcpyAsync(h_indeg.data(), indeg, M * sizeof(uint32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+          hipStreamSynchronize(stream) != hipSuccess)
+        throw std::runtime_error("CommunityCores: reading the inner degrees back failed");
+      std::vector<uint64_t> nbr_off(M + 1, 0);
+      for (uint64_t s = 0; s < M; ++s) nbr_off[s + 1] = nbr_off[s] + h_indeg[s];
+      r.L = nbr_off[M];
+      if (r.L >= AMMSB_CORES_MAX_NBR || 4 * r.L > max_bytes)
+        throw std::invalid_argument("CommunityCores: the induced subgraphs hold " + std::to_string(r.L) +
+                                    " neighbour entries at the threshold " + G9(threshold) + ", " + std::to_string(4 * r.L) +
+                                    " bytes; the library takes fewer than 2^32 entries and max_bytes is " +
+                                    std::to_string(max_bytes) + " (raise the threshold)");
+      clcuda::Buffer<uint64_t> d_nbr_off(context, queue_, nbr_off.begin(), nbr_off.end());
+      clcuda::Buffer<uint32_t> d_nbr(context, std::max<uint64_t>(r.L, 1));
+      rc = ammsb_cores_adjacency(d_mask(), N, cols, d_base(), M, d_offsets(), d_targets(), 0, N, indeg, d_nbr_off(), r.L, d_nbr(),
+                                 stream);
+      if (rc != AMMSB_OK) throw PostfitError("ammsb_cores_adjacency", rc, ammsb_cores_last_error());
+      if (hipMemcpyAsync(deg, indeg, M * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+        throw std::runtime_error("CommunityCores: copying the inner degrees failed");
+      // the host loop of the header: 12 bytes back after every launch, at most M peel launches
+      struct {
+        uint64_t tail;
+        uint32_t next;
+      } ctl = {0, 0};
+      const auto read = [&]() {
+        if (hipMemcpyAsync(&ctl, tail_p, 12, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+          throw std::runtime_error("CommunityCores: reading the queue's tail back failed");
+      };
+      uint64_t head = 0;
+      uint32_t level = 0;
+      const uint32_t none = 0xFFFFFFFFu;
+      for (;;) {
+        if (hipMemcpyAsync(next_p, &none, 4, hipMemcpyHostToDevice, stream) != hipSuccess)
+          throw std::runtime_error("CommunityCores: resetting next_level failed");
+        rc = ammsb_cores_scan(M, level, deg, queue, tail_p, next_p, counts, stream);
+        if (rc != AMMSB_OK) throw PostfitError("ammsb_cores_scan", rc, ammsb_cores_last_error());
+        read();
+        if (ctl.tail == head) {  // nothing at this level
+          if (ctl.tail >= M || ctl.next == none) break;
+          level = ctl.next;  // (no peel ran since the scan: the smallest degree left)
+          continue;
+        }
+        if (level == 0) head = ctl.tail;  // (a slot of degree 0 has no row: nothing to lower)
+        while (head < ctl.tail) {
+          rc = ammsb_cores_peel(M, level, head, ctl.tail, d_nbr_off(), indeg, d_nbr(), r.L, deg, queue, tail_p, counts, stream);
+          if (rc != AMMSB_OK) throw PostfitError("ammsb_cores_peel", rc, ammsb_cores_last_error());
+          head = ctl.tail;
+          read();
+          if (ctl.tail > M) throw std::runtime_error("CommunityCores: the queue holds more slots than there are");
+        }
+        if (ctl.tail >= M) break;
+        ++level;
+      }
+      if (ctl.tail != M) throw std::runtime_error("CommunityCores: the peel ended before every slot was queued");
+    }
+    rc = ammsb_cores_finish(N, cols, d_base(), M, d_comm(), indeg, deg, d_sums(), d_sums() + K, d_top(), d_sums() + 2 * K,
+                            d_sums() + 3 * K, d_node + N, reinterpret_cast<int32_t*>(d_node + 2 * N), d_node + 3 * N,
+                            stream);
+    if (rc != AMMSB_OK) throw PostfitError("ammsb_cores_finish", rc, ammsb_cores_last_error());
+    std::vector<uint64_t> sums(4 * K + 6);
+    std::vector<uint32_t> slot(3 * m1), node(4 * N);
+    r.community.resize(m1);
+    r.degeneracy.resize(K);
+    d_sums.Read(queue_, 4 * K + 6, sums.data());
+    d_top.Read(queue_, K, r.degeneracy.data());
+    d_slot.Read(queue_, 3 * m1, slot.data());
+    d_comm.Read(queue_, m1, r.community.data());
+    d_node4.Read(queue_, 4 * N, node.data());
+    queue_.Finish();
+    r.community.resize(M);
+    r.core.assign(slot.begin() + m1, slot.begin() + m1 + M);
+    r.indeg.assign(slot.begin() + 2 * m1, slot.begin() + 2 * m1 + M);
+    r.best_core.assign(node.begin() + N, node.begin() + 2 * N);
+    for (uint64_t a = 0; a < N; ++a) r.best_comm[a] = static_cast<int32_t>(node[2 * N + a]);
+    r.in_nucleus.assign(node.begin() + 3 * N, node.end());
+    r.members.assign(sums.begin(), sums.begin() + K);
+    r.inlinks2.assign(sums.begin() + K, sums.begin() + 2 * K);
+    r.nucleus.assign(sums.begin() + 2 * K, sums.begin() + 3 * K);
+    r.isolated.assign(sums.begin() + 3 * K, sums.begin() + 4 * K);
+    if (sums[4 * K] != M || sums[4 * K + 1] != r.L) throw std::runtime_error("CommunityCores: the device's counts contradict the arrays");
+    r.scans = sums[4 * K + 2];
+    r.rounds = sums[4 * K + 3];
+  }
+  r.Derive();
+}
+
+bool Learner::WriteCommunityCores(std::ostream* out, Float threshold, const std::vector<Edge>* edges) {
+  CoresResult r;
+  CommunityCores(threshold, &r, edges);
+  *out << "# " << pi_->Rows() << " " << pi_->Cols() << " " << r.core.size() << " " << r.L << " " << G9(threshold) << " " << r.skipped
+       << " " << r.dropped << "\n";
+  for (size_t k = 0; k < r.members.size(); ++k)
+    *out << "c " << k << " " << r.members[k] << " " << r.inlinks2[k] << " " << r.degeneracy[k] << " " << r.nucleus[k] << " "
+         << r.isolated[k] << "\n";
+  for (size_t a = 0; a + 1 < r.offsets.size(); ++a) {
+    *out << "n " << a << " " << r.offsets[a + 1] - r.offsets[a];
+    for (uint64_t s = r.offsets[a]; s < r.offsets[a + 1]; ++s) *out << " " << r.community[s] << " " << r.indeg[s] << " " << r.core[s];
     *out << "\n";
   }
   return static_cast<bool>(*out);

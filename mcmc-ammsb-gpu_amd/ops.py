@@ -1669,6 +1669,202 @@ class CommunityComponents:
         return self.cc.last_kernel_name()
 
 
+class CommunityCores:
+    """The k-core decomposition of every detected community (include/ammsb_cores.h): over CommunityLinks' node-major
+    membership bits, the slot numbering of CommunityComponents and a simple CSR adjacency, two passes build the induced slot
+    graph (the inner degree of every membership, then its neighbours' slots in row order), a level-synchronous peel lowers
+    the degrees to the core numbers -- one launch per sub-round, 12 bytes read back between launches, no lane ever waiting
+    for another -- and a finish pass reduces them per community and per node.  Integers that the cover and the adjacency
+    alone determine: exact, and independent of the kernel form, the order in which the queue fills and how the node range of
+    the build passes is cut into calls.  Owns nothing but the tensors it returns."""
+
+    PER_COMMUNITY = (("members", torch.int64), ("inlinks2", torch.int64), ("degeneracy", torch.int32), ("nucleus", torch.int64),
+                     ("isolated", torch.int64))
+    PER_NODE = (("best_core", torch.int32), ("best_comm", torch.int32), ("in_nucleus", torch.int32))
+
+    def __init__(self, ctx):
+        from . import _cores
+        self.ctx = ctx
+        self.co = _cores
+        self.lib = _cores.load()
+        self.comp = CommunityComponents(ctx)
+        self.links = self.comp.links
+
+    def _check(self, mask, N, K, base, M, offsets, targets):
+        _check_mask(mask, N, K, "cores")
+        if base.dtype != torch.int64 or not base.is_contiguous() or base.numel() != N + 1:
+            raise AmmsbError("cores: base must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
+        if offsets.dtype != torch.int64 or not offsets.is_contiguous() or offsets.numel() != N + 1:
+            raise AmmsbError("cores: offsets must be a contiguous [N + 1] int64 (uint64 bits) device tensor")
+        if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 1:
+            raise AmmsbError("cores: targets must be a contiguous 1-d int32 (uint32 bits) device tensor")
+        if N and int(offsets[-1]) > targets.numel():
+            raise AmmsbError("cores: the offsets end past the targets")
+
+    @staticmethod
+    def _range(N, first, count):
+        first = int(first)
+        count = N - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > N:
+            raise AmmsbError("cores: the nodes %d .. %d are not inside 0 .. %d" % (first, first + count, N))
+        return first, count
+
+    def _per_slot(self, t, M, what):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != M:
+            raise AmmsbError("cores: %s must be a contiguous [M] int32 (uint32 bits) device tensor" % what)
+
+    def degrees(self, mask, N, K, base, M, offsets, targets, first=0, count=None, indeg=None, counts=None):
+        """the inner degree of every slot of the nodes first .. first + count - 1 (default: through N - 1) into indeg [M]
+        int32 (uint32 bits), and their slots and inner degrees added to counts [4] int64 (M, L, scans, rounds); either is made
+        (indeg uninitialised, counts zeroed) where none is given; calls over disjoint ranges fill one indeg
+        -> (indeg, counts)"""
+        N, K, M = int(N), int(K), self.co.check_slots(M)
+        first, count = self._range(N, first, count)
+        self._check(mask, N, K, base, M, offsets, targets)
+        indeg = self.ctx.empty((M,), torch.int32) if indeg is None else indeg
+        counts = self.ctx.zeros((4,), torch.int64) if counts is None else counts
+        self._per_slot(indeg, M, "indeg")
+        if counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != 4:
+            raise AmmsbError("cores: counts must be a contiguous [4] int64 device tensor")
+        if count and M:  # (an empty range is a valid no-op; an empty tensor has no address)
+            tgt = targets if targets.numel() else self.ctx.zeros((1,), torch.int32)
+            self.co.check(self.lib.ammsb_cores_degrees(_ptr(mask), N, K, _ptr(base), M, _ptr(offsets), _ptr(tgt), first, count,
+                                                       _ptr(indeg), _ptr(counts), _stream()))
+        return indeg, counts
+
+    def offsets(self, indeg, max_bytes=None, threshold=None):
+        """indeg -> (nbr_off [M + 1] int64, the exclusive prefix sum by a torch cumsum in int64, L = nbr_off[M]); waits for L
+        and refuses L >= 2^32 or 4 L > max_bytes (default 4 GiB) before anything is allocated for nbr"""
+        nbr_off = torch.zeros(indeg.numel() + 1, dtype=torch.int64, device=indeg.device)
+        if indeg.numel():
+            torch.cumsum(indeg.to(torch.int64) & 0xFFFFFFFF, 0, out=nbr_off[1:])
+        return nbr_off, self.co.check_links(int(nbr_off[-1]), self.co.MAX_BYTES if max_bytes is None else max_bytes, threshold)
+
+    def adjacency(self, mask, N, K, base, M, offsets, targets, indeg, nbr_off, L, first=0, count=None, nbr=None):
+        """the rows of nbr [L] int32 (uint32 bits) of the nodes first .. first + count - 1 (default: through N - 1); nbr is
+        made, uninitialised, where none is given -> nbr"""
+        N, K, M, L = int(N), int(K), self.co.check_slots(M), int(L)
+        first, count = self._range(N, first, count)
+        self._check(mask, N, K, base, M, offsets, targets)
+        self._per_slot(indeg, M, "indeg")
+        if nbr_off.dtype != torch.int64 or not nbr_off.is_contiguous() or nbr_off.numel() != M + 1:
+            raise AmmsbError("cores: nbr_off must be a contiguous [M + 1] int64 (uint64 bits) device tensor")
+        if L < 0 or L >= self.co.MAX_NBR:
+            raise AmmsbError("cores: %d entries of nbr; the library takes fewer than 2^32" % L)
+        nbr = self.ctx.empty((L,), torch.int32) if nbr is None else nbr
+        if nbr.dtype != torch.int32 or not nbr.is_contiguous() or nbr.numel() != L:
+            raise AmmsbError("cores: nbr must be a contiguous [L] int32 (uint32 bits) device tensor")
+        if count and M and L:
+            self.co.check(self.lib.ammsb_cores_adjacency(_ptr(mask), N, K, _ptr(base), M, _ptr(offsets), _ptr(targets), first,
+                                                         count, _ptr(indeg), _ptr(nbr_off), L, _ptr(nbr), _stream()))
+        return nbr
+
+    def state(self, N, K, M, indeg, counts=None):
+        """-> the buffers of one peel and finish for an N x K pi with M slots: name -> device tensor (uint32 as int32, uint64
+        as int64); deg [M], a copy of indeg that the peel lowers to the core numbers; queue [M]; ctl [2] int64 (tail, then
+        next_level in the low half of the second word); members, inlinks2, degeneracy, nucleus, isolated [K], zeroed;
+        best_core, best_comm, in_nucleus [N]; counts [4]"""
+        self._per_slot(indeg, M, "indeg")
+        out = {"deg": indeg.clone(), "queue": self.ctx.empty((M,), torch.int32), "ctl": self.ctx.zeros((2,), torch.int64)}
+        out.update({name: self.ctx.zeros((K,), dtype) for name, dtype in self.PER_COMMUNITY})
+        out.update({name: self.ctx.zeros((N,), dtype) for name, dtype in self.PER_NODE})
+        out["counts"] = self.ctx.zeros((4,), torch.int64) if counts is None else counts
+        return out
+
+    def peel(self, M, indeg, nbr_off, nbr, state, num_nbr=None):
+        """the host loop of the header over state["deg"]: scan a level, peel its queue launch by launch, read tail and
+        next_level back (12 bytes) after every launch; ends when every slot is queued.  nbr holds num_nbr entries (default:
+        all of it); rows need not be packed -> (scans, rounds) of this call"""
+        M = self.co.check_slots(M)
+        num_nbr = int(nbr.numel() if num_nbr is None else num_nbr)
+        deg, queue, ctl, counts = state["deg"], state["queue"], state["ctl"], state["counts"]
+        for t, what in ((indeg, "indeg"), (deg, "deg"), (queue, "queue")):
+            self._per_slot(t, M, what)
+        if nbr.dtype != torch.int32 or not nbr.is_contiguous() or num_nbr > nbr.numel() or num_nbr >= self.co.MAX_NBR:
+            raise AmmsbError("cores: nbr must be a contiguous int32 (uint32 bits) device tensor of fewer than 2^32 entries")
+        if nbr_off.dtype != torch.int64 or not nbr_off.is_contiguous() or nbr_off.numel() < M:
+            raise AmmsbError("cores: nbr_off must be a contiguous int64 (uint64 bits) device tensor of at least M entries")
+        if not M:
+            return 0, 0
+        tail_p, next_p = C.c_void_p(ctl.data_ptr()), C.c_void_p(ctl.data_ptr() + 8)
+        none = 0xFFFFFFFF
+        reset = torch.tensor([0, none], dtype=torch.int64, device=ctl.device)
+        ctl.copy_(reset)
+        scans = rounds = 0
+        level = head = 0
+
+        def read():
+            got = ctl.cpu().numpy().view(np.uint32)   # (tail's two halves, next_level)
+            return int(got[0]) | (int(got[1]) << 32), int(got[2])
+
+        def scan(level, tail):
+            reset[0] = tail
+            ctl.copy_(reset)    # (next_level back to "none"; tail as it is)
+            self.co.check(self.lib.ammsb_cores_scan(M, level, _ptr(deg), _ptr(queue), tail_p, next_p, _ptr(counts), _stream()))
+            return read()
+
+        tail = 0
+        while True:
+            tail, nxt = scan(level, tail)
+            scans += 1
+            if tail == head:                       # nothing at this level
+                if tail >= M or nxt == none:
+                    break
+                level = nxt                        # (no peel ran since the scan: the smallest degree left)
+                continue
+            if level == 0:
+                head = tail                        # (a slot of degree 0 has no row: nothing to lower)
+            while head < tail:
+                nb = _ptr(nbr) if nbr.numel() else None
+                self.co.check(self.lib.ammsb_cores_peel(M, level, head, tail, _ptr(nbr_off), _ptr(indeg), nb, num_nbr, _ptr(deg),
+                                                        _ptr(queue), tail_p, _ptr(counts), _stream()))
+                rounds += 1
+                head = tail
+                tail, _ = read()
+                if tail > M:
+                    raise AmmsbError("cores: the queue holds %d slots of %d" % (tail, M))
+            if tail >= M:
+                break
+            level += 1
+        if tail != M:
+            raise AmmsbError("cores: the peel ended with %d of %d slots queued" % (tail, M))
+        return scans, rounds
+
+    def finish(self, N, K, base, M, slot_comm, indeg, state):
+        """after peel(): the K- and N-sized arrays of the state from indeg and core = state["deg"] -> state"""
+        N, K, M = int(N), int(K), self.co.check_slots(M)
+        if M and (slot_comm.dtype != torch.int16 or not slot_comm.is_contiguous() or slot_comm.numel() != M):
+            raise AmmsbError("cores: slot_comm must be a contiguous [M] int16 (uint16 bits) device tensor")
+        slot = lambda t: _ptr(t) if M else None   # noqa: E731  (an empty tensor has no address)
+        node = lambda name: _ptr(state[name]) if N else None   # noqa: E731
+        self.co.check(self.lib.ammsb_cores_finish(
+            N, K, _ptr(base), M, slot(slot_comm), slot(indeg), slot(state["deg"]), _ptr(state["members"]),
+            _ptr(state["inlinks2"]), _ptr(state["degeneracy"]), _ptr(state["nucleus"]), _ptr(state["isolated"]),
+            node("best_core"), node("best_comm"), node("in_nucleus"), _stream()))
+        return state
+
+    def run(self, pi, thr, offsets, targets, max_bytes=None, mask=None):
+        """-> (state, base, M, slot_comm, indeg, nbr_off, nbr) for the cover (pi, thr) and the simple CSR; the core numbers
+        are state["deg"]"""
+        N, K = int(pi.desc.num_rows), int(pi.cols)
+        thr = self.co.check_threshold(thr)
+        mask = self.links.mask(pi, thr) if mask is None else mask
+        base, M = self.comp.base(self.comp.own(mask, N, K), thr)
+        self.co.check_slots(M, thr)
+        slots = self.comp.slots(mask, N, K, base, M, self.comp.state(N, K, M))
+        slot_comm = slots["slot_comm"]
+        del slots
+        indeg, counts = self.degrees(mask, N, K, base, M, offsets, targets)
+        nbr_off, L = self.offsets(indeg, max_bytes, thr)
+        nbr = self.adjacency(mask, N, K, base, M, offsets, targets, indeg, nbr_off, L)
+        state = self.state(N, K, M, indeg, counts)
+        self.peel(M, indeg, nbr_off, nbr, state)
+        return self.finish(N, K, base, M, slot_comm, indeg, state), base, M, slot_comm, indeg, nbr_off, nbr
+
+    def kernel_name(self):
+        return self.co.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 

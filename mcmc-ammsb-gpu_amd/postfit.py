@@ -495,13 +495,16 @@ class PostFit:
     def _triangles(self):
         return self._postfit_op("_triangles_op", "Triangles", "the triangles")
 
-    def _simple_csr(self, edges):
+    def _simple_csr(self, edges, row_limit=True):
         """keys (a << 32) | b, or None for the training links -> (offsets [N + 1] int64, targets int32, M, skipped,
         dropped): the simple symmetric adjacency of the list, built on the device -- both directions of every key with both
         ends < N as 64-bit keys, sorted, made unique, loops removed; skipped counts the keys with an end >= N, dropped the
-        repeats (in either order) and loops.  That of the training links is built once and kept."""
+        repeats (in either order) and loops.  That of the training links is built once and kept.  row_limit: refuse a row
+        longer than the triangles library takes."""
         from . import _triangles
         if edges is None and getattr(self, "_training_simple_csr", None) is not None:
+            if row_limit:
+                _triangles.check_rows(self._training_simple_longest)
             return self._training_simple_csr
         N = self.cfg.N
         if N >= 2 ** 31:
@@ -516,14 +519,16 @@ class PostFit:
         both = both[(both >> 32) != (both & 0xFFFFFFFF)]
         src = both >> 32
         rows = torch.bincount(src, minlength=N)
-        _triangles.check_rows(int(rows.max()) if N else 0)
+        longest = int(rows.max()) if N else 0
+        if row_limit:
+            _triangles.check_rows(longest)
         offsets = torch.zeros(N + 1, dtype=torch.int64, device=keys.device)
         offsets[1:] = torch.cumsum(rows, 0)
         M = int(both.numel())
         out = (offsets, (both & 0xFFFFFFFF).to(torch.int32).contiguous(), M, int(keys.numel() - a.numel()),
                int(a.numel()) - M // 2)
         if edges is None:
-            self._training_simple_csr = out
+            self._training_simple_csr, self._training_simple_longest = out, longest
         return out
 
     def Triangles(self, threshold=0.05, edges=None, nodes=None):
@@ -580,3 +585,34 @@ class PostFit:
                                       h("largest_root", np.int32), h("singletons", np.uint64), base.cpu().numpy().view(np.uint64),
                                       h("slot_comm", np.uint16), h("root", np.uint32), h("size", np.uint32), h("stray", np.uint32),
                                       valid, skipped, shared)
+
+    # ---- where does a node sit inside a community? (include/ammsb_cores.h)
+    def _cores(self):
+        return self._postfit_op("_cores_op", "CommunityCores", "the community cores")
+
+    def CommunityCores(self, threshold=0.05, edges=None, max_bytes=4 << 30):
+        """-> _cores.Cores: the k-core decomposition of the subgraph every community of the cover pi[a, k] >= threshold
+        induces in a simple adjacency: that of the training links (edges=None), or that of `edges` (host array or device
+        tensor of (a << 32) | b; repeats and loops counted in .dropped, a key with an end >= N in .skipped; a row may have
+        any length).  .members, .inlinks2, .degeneracy, .nucleus, .isolated per community; the memberships as a CSR over the
+        nodes, .offsets [N + 1] and .community, .indeg, .core [M]; .best_core, .best_comm, .in_nucleus [N]; .M, .L, .skipped,
+        .dropped, all exact integers, and the launch counts .scans and .rounds; .coreness [M], .nucleus_share, .mean_core
+        [K] in float64 on the host; .shells(k), .cover(c), .nuclei(), .fringe(c).  A cover of 2^32 memberships or more, and
+        induced subgraphs whose neighbour lists take 2^32 entries or more than max_bytes, are refused before the peel."""
+        from . import _cores
+        threshold = _cores.check_threshold(threshold)
+        _cores.check_nodes(self.cfg.N)
+        op = self._cores()
+        self.drain()
+        offsets, targets, _, skipped, dropped = self._simple_csr(edges, row_limit=False)
+        st, base, M, slot_comm, indeg, _, _ = op.run(self.pi, threshold, offsets, targets, max_bytes)
+        counts = [int(v) for v in st["counts"].cpu().numpy().view(np.uint64)]
+        h = lambda t, dt: t.cpu().numpy().view(dt)   # noqa: E731
+        r = _cores.Cores(threshold, h(st["members"], np.uint64), h(st["inlinks2"], np.uint64), h(st["degeneracy"], np.uint32),
+                         h(st["nucleus"], np.uint64), h(st["isolated"], np.uint64), h(base, np.uint64), h(slot_comm, np.uint16),
+                         h(indeg, np.uint32), h(st["deg"], np.uint32), h(st["best_core"], np.uint32), h(st["best_comm"], np.int32),
+                         h(st["in_nucleus"], np.uint32), skipped, dropped, counts[2], counts[3])
+        if (counts[0], counts[1]) != (r.M, r.L):
+            raise AmmsbError("cores: the device counted %d slots and %d neighbour entries, the arrays hold %d and %d"
+                             % (counts[0], counts[1], r.M, r.L))
+        return r
