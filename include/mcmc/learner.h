@@ -36,6 +36,23 @@ class Learner {
   std::vector<Float> GetPiRow(Vertex v);
   uint64_t MiniBatchEdges() const { return edges_done_; }
 
+  // Averaging over the chain (include/ammsb_average.h; not in the reference API).  From StartAverage() on the learner keeps
+  // the mean of (pi, beta) over the iterations: sample t is the state after the t-th Step since.  The mean of pi is lazy -- a
+  // row is brought up to date just before an iteration overwrites it (first thing in Step) and once more when the mean is
+  // read -- and costs a second pi in device memory; beta's mean is kept in binary64 (last thing in Step).  Both the
+  // synchronous and the async loop keep it.  StartAverage() again sets the count back to 0; Parse() ends the average (the
+  // checkpoint does not carry it).  Throws std::invalid_argument under Config::graph_launch and when the run is sharded.
+  void StartAverage();
+  void StopAverage();
+  uint32_t AverageSamples() const { return averaging_ ? avg_n_ : 0; }
+  // the mean of beta rounded to binary32 once, and a row of the mean of pi; both flush first and throw std::runtime_error
+  // while no sample exists
+  std::vector<Float> GetMeanBeta();
+  std::vector<Float> GetMeanPiRow(Vertex v);
+  // While set, every post-fit method below reads the flushed mean of (pi, beta) instead of the last draw (and throws
+  // std::runtime_error while no sample exists).  Off by default.
+  void ReadAverage(bool on) { read_average_ = on; }
+
   // Reading the model out (include/ammsb_readout.h; not in the reference API).  Per node its `top` (1..16) strongest
   // communities, value descending and equal values by community ascending: ids / weights are [N, top], a slot below
   // `threshold` (>= 0) or past K holds 0xFFFFFFFF / 0; count[a] = communities >= threshold, not capped at top;
@@ -349,6 +366,11 @@ class Learner {
   void StepSharded(Sample& s, Float weight);
   Float Perplexity(PerplexityCalculator* calc);
   void GatherShardedState();  // before a checkpoint: owners hand out their phi streams and running means
+  // The (pi, beta) a post-fit method reads, called after it has drained the loop: the last draw, or under ReadAverage(true)
+  // the mean with every row flushed (host/postfit.cc)
+  const ammsb_rpm& PostfitPi();
+  const Float* PostfitBeta();
+  void FlushAverage();  // every row of mean_pi_ and mean_beta_ up to avg_n_; nothing is launched when nothing ran since
 
   const Config& cfg_;
   clcuda::Queue queue_;
@@ -410,6 +432,13 @@ class Learner {
   double calib_phi_ms_ = 0, calib_xchg_ms_ = 0;
   std::unique_ptr<clcuda::Buffer<Float>> all_grads_, grads_sum_, tail_buf_;
   std::unique_ptr<clcuda::Buffer<ammsb_ppx_sums>> all_sums_;
+  // the chain average: mean_pi_[a, :] is the mean of the samples 1 .. avg_last_[a], and the samples after that equal pi
+  bool averaging_ = false, read_average_ = false;
+  uint32_t avg_n_ = 0, avg_flushed_ = 0;
+  std::unique_ptr<RowPartitionedMatrix<Float>> mean_pi_;
+  std::unique_ptr<clcuda::Buffer<uint32_t>> avg_last_;
+  std::unique_ptr<clcuda::Buffer<double>> mean_beta64_;
+  std::unique_ptr<clcuda::Buffer<Float>> mean_beta_;
   std::unique_ptr<Sample> samples_[2];  // MCMC_SAMPLE_PARALLEL (CMakeLists.txt:42, default ON)
   std::future<Float> futures_[2];
   int phase_;

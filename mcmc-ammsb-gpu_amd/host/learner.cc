@@ -7,6 +7,7 @@
 #include "mcmc/exchange.h"
 #include "mcmc/serialize.h"
 #include "ammsb_refsample.h"
+#include "ammsb_average.h"
 
 #include <hip/hip_runtime.h>
 
@@ -411,8 +412,81 @@ bool Learner::Sharded() const { return cfg_.exchange && cfg_.exchange->world() >
 
 void Learner::Step(Sample& s, Float weight) {
   if (Sharded()) return StepSharded(s, weight);
+  if (averaging_ && avg_n_) {  // the rows this step overwrites: their mean is brought up to the samples so far first
+    const int rc = ammsb_average_rows(&pi_->Get(), &mean_pi_->Get(), avg_last_->data(), s.dev_nodes.data(), 0, s.num_nodes,
+                                      avg_n_, queue_.stream());
+    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_rows: ") + ammsb_average_last_error());
+  }
   phiUpdater_(s.dev_nodes, s.neighbor_sampler.GetData(), s.num_nodes);
   betaUpdater_(&s.dev_edges, s.num_edges, weight);
+  if (averaging_) {
+    const int rc = ammsb_average_vector(beta_.data(), mean_beta64_->data(), 2 * cfg_.K, ++avg_n_, queue_.stream());
+    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_vector: ") + ammsb_average_last_error());
+  }
+}
+
+// ---- the chain average (include/ammsb_average.h)
+void Learner::StartAverage() {
+  if (cfg_.graph_launch)
+    throw std::invalid_argument("StartAverage: the chain average is kept by the eager loops, not under graph_launch");
+  if (Sharded()) throw std::invalid_argument("StartAverage: the chain average covers one rank");
+  DrainAsync();
+  queue_.Finish();
+  if (!mean_pi_) {
+    const clcuda::Context context = queue_.GetContext();
+    mean_pi_.reset(allocFactory_->CreateMatrix(pi_->Rows(), pi_->Cols(), pi_->RowsPerBlock()));
+    avg_last_.reset(new clcuda::Buffer<uint32_t>(context, pi_->Rows()));
+    mean_beta64_.reset(new clcuda::Buffer<double>(context, 2 * cfg_.K));
+    mean_beta_.reset(new clcuda::Buffer<Float>(context, 2 * cfg_.K));
+  }
+  clcuda::Check(hipMemsetAsync(avg_last_->data(), 0, avg_last_->GetSize(), static_cast<hipStream_t>(queue_.stream())),
+                "hipMemsetAsync");
+  avg_n_ = avg_flushed_ = 0;
+  averaging_ = true;
+}
+
+void Learner::StopAverage() {
+  DrainAsync();
+  queue_.Finish();
+  averaging_ = false;
+  avg_n_ = avg_flushed_ = 0;
+  mean_pi_.reset();
+  avg_last_.reset();
+  mean_beta64_.reset();
+  mean_beta_.reset();
+}
+
+void Learner::FlushAverage() {
+  if (!averaging_ || avg_n_ == 0) throw std::runtime_error("the chain average holds no sample (StartAverage, then Run)");
+  if (avg_flushed_ == avg_n_) return;
+  const uint64_t N = pi_->Rows(), slab = std::max<uint64_t>(1, (256ull << 20) / (sizeof(Float) * pi_->Cols()));
+  for (uint64_t lo = 0; lo < N; lo += slab) {
+    const int rc = ammsb_average_rows(&pi_->Get(), &mean_pi_->Get(), avg_last_->data(), nullptr, lo, std::min(slab, N - lo),
+                                      avg_n_, queue_.stream());
+    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_rows: ") + ammsb_average_last_error());
+  }
+  const int rc = ammsb_average_round(mean_beta64_->data(), mean_beta_->data(), 2 * cfg_.K, queue_.stream());
+  if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_round: ") + ammsb_average_last_error());
+  avg_flushed_ = avg_n_;
+}
+
+std::vector<Float> Learner::GetMeanBeta() {
+  DrainAsync();
+  queue_.Finish();
+  FlushAverage();
+  std::vector<Float> v(2 * cfg_.K);
+  mean_beta_->Read(queue_, v.size(), v.data());
+  return v;
+}
+
+std::vector<Float> Learner::GetMeanPiRow(Vertex v) {
+  DrainAsync();
+  queue_.Finish();
+  FlushAverage();
+  std::vector<Float> row(cfg_.K);
+  const uint32_t blk = v / mean_pi_->RowsPerBlock();
+  mean_pi_->Blocks()[blk].Read(queue_, cfg_.K, row.data(), (size_t)(v % mean_pi_->RowsPerBlock()) * cfg_.K);
+  return row;
 }
 
 // Where pi lands in HBM (mcmc-ammsb-gpu_amd/learner.py, _place_pi): update_phi gathers 4 KiB rows of pi at random, and
@@ -961,6 +1035,7 @@ bool Learner::ParseDeviceSampler(std::istream* in) {
 bool Learner::Parse(std::istream* in) {
   for (auto& f : futures_)
     if (f.valid()) f.wait();
+  StopAverage();  // the checkpoint does not carry it
   LearnerProperties props;
   if (!(::mcmc::Parse(in, &beta_, &queue_) && ::mcmc::Parse(in, &theta_, &queue_) &&
         ::mcmc::Parse(in, pi_.get(), &queue_) && ::mcmc::Parse(in, &phi_, &queue_) && phiUpdater_.Parse(in) &&

@@ -96,6 +96,20 @@ clcuda::Buffer<uint64_t> MembershipMask(const char* call, const ammsb_rpm* pi, F
 }
 }  // namespace
 
+// ---- what the analyses read: the last draw, or under ReadAverage(true) the chain average with every row flushed.  Every
+// method calls these after it has drained the loop, so the flush is enqueued behind the last iteration.
+const ammsb_rpm& Learner::PostfitPi() {
+  if (!read_average_) return pi_->Get();
+  FlushAverage();
+  return mean_pi_->Get();
+}
+
+const Float* Learner::PostfitBeta() {
+  if (!read_average_) return beta_.data();
+  FlushAverage();
+  return mean_beta_->data();
+}
+
 // ---- reading the model out: libammsb_readout.so over pi, in row slabs whose outputs stay under a fixed byte budget
 void Learner::Memberships(uint32_t top, Float threshold, std::vector<uint32_t>* ids, std::vector<Float>* weights,
                           std::vector<uint32_t>* count, std::vector<uint64_t>* sizes) {
@@ -119,7 +133,7 @@ void Learner::Memberships(uint32_t top, Float threshold, std::vector<uint32_t>* 
   if (count) count->resize(N);
   for (uint64_t lo = 0; lo < N; lo += slab) {
     const uint64_t n = std::min(slab, N - lo);
-    const int rc = ammsb_readout_top(&pi_->Get(), nullptr, lo, n, top, threshold, tops ? d_ids() : nullptr,
+    const int rc = ammsb_readout_top(&PostfitPi(), nullptr, lo, n, top, threshold, tops ? d_ids() : nullptr,
                                      tops ? d_weights() : nullptr, tops ? d_count() : nullptr,
                                      d_sizes ? (*d_sizes)() : nullptr, queue_.stream());
     if (rc != AMMSB_OK)
@@ -173,7 +187,7 @@ void Learner::LinkProbabilities(const std::vector<Edge>& edges, std::vector<Floa
   const clcuda::Context context = queue_.GetContext();
   clcuda::Buffer<Edge> d_edges(context, queue_, edges.begin(), edges.end());
   clcuda::Buffer<Float> d_out(context, edges.size());
-  const int rc = ammsb_linkpred_pairs(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), edges.size(),
+  const int rc = ammsb_linkpred_pairs(&PostfitPi(), PostfitBeta(), MakeKernelParams(cfg_).epsilon, d_edges(), edges.size(),
                                       d_out(), queue_.stream());
   if (rc != AMMSB_OK)
     throw PostfitError("ammsb_linkpred_pairs", rc, ammsb_linkpred_last_error());
@@ -207,7 +221,7 @@ void Learner::PredictLinks(const std::vector<Vertex>& nodes, uint32_t top, uint3
   const Float eps = MakeKernelParams(cfg_).epsilon;
   for (uint64_t lo = 0; lo < Q; lo += slab) {
     const uint64_t n = std::min(slab, Q - lo);
-    const int rc = ammsb_linkpred_top(&pi_->Get(), beta_.data(), eps, d_nodes() + lo, static_cast<uint32_t>(n), top, ex[0],
+    const int rc = ammsb_linkpred_top(&PostfitPi(), PostfitBeta(), eps, d_nodes() + lo, static_cast<uint32_t>(n), top, ex[0],
                                       ex[1], 0, N, d_ids(), d_scores(), d_ws(), ws_bytes, queue_.stream());
     if (rc != AMMSB_OK)
       throw PostfitError("ammsb_linkpred_top", rc, ammsb_linkpred_last_error());
@@ -279,7 +293,7 @@ void Learner::LinkCommunities(const std::vector<Edge>& edges, uint32_t top, Floa
   const Float eps = MakeKernelParams(cfg_).epsilon;
   for (uint64_t lo = 0; lo < n_all; lo += slab) {
     const uint64_t n = std::min(slab, n_all - lo);
-    const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), eps, d_edges() + lo, n, top, min_term, d_ids(),
+    const int rc = ammsb_linkcomm_edges(&PostfitPi(), PostfitBeta(), eps, d_edges() + lo, n, top, min_term, d_ids(),
                                         d_terms(), d_prob(), nullptr, queue_.stream());
     if (rc != AMMSB_OK)
       throw PostfitError("ammsb_linkcomm_edges", rc, ammsb_linkcomm_last_error());
@@ -301,7 +315,7 @@ void Learner::LinkCommunitySizes(Float min_term, std::vector<uint64_t>* sizes) {
   const clcuda::Context context = queue_.GetContext();
   clcuda::Buffer<Edge> d_edges(context, queue_, links.begin(), links.end());
   clcuda::Buffer<uint64_t> d_sizes(context, queue_, sizes->begin(), sizes->end());
-  const int rc = ammsb_linkcomm_edges(&pi_->Get(), beta_.data(), MakeKernelParams(cfg_).epsilon, d_edges(), links.size(), 1,
+  const int rc = ammsb_linkcomm_edges(&PostfitPi(), PostfitBeta(), MakeKernelParams(cfg_).epsilon, d_edges(), links.size(), 1,
                                       min_term, nullptr, nullptr, nullptr, d_sizes(), queue_.stream());
   if (rc != AMMSB_OK)
     throw PostfitError("ammsb_linkcomm_edges", rc, ammsb_linkcomm_last_error());
@@ -343,7 +357,7 @@ void Learner::CommunityQuality(Float threshold, std::vector<uint64_t>* size, std
   clcuda::Buffer<Edge> d_edges(context, queue_, links.begin(), links.end());
   std::vector<uint64_t> counts(2 * K + 2, 0);
   clcuda::Buffer<uint64_t> d_counts(context, queue_, counts.begin(), counts.end());
-  int rc = ammsb_quality_mask(&pi_->Get(), threshold, d_mask(), queue_.stream());
+  int rc = ammsb_quality_mask(&PostfitPi(), threshold, d_mask(), queue_.stream());
   if (rc == AMMSB_OK)
     rc = ammsb_quality_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), links.size(), d_counts(), nullptr,
                              queue_.stream());
@@ -422,7 +436,7 @@ void Learner::CompareCover(const std::vector<uint64_t>& offsets, const std::vect
     clcuda::Buffer<uint32_t> d_tover(context, G), d_tsize(context, G), d_dover(context, K);
     clcuda::Buffer<uint32_t> d_dense(context, overlap ? G * K : 1);
     clcuda::Buffer<uint64_t> d_skipped(context, 1), d_ws(context, (ws_bytes + 7) / 8);
-    const int rc = ammsb_cover_match(&pi_->Get(), threshold, d_offsets(), G, d_members(), M, d_dsize(), d_tbest(),
+    const int rc = ammsb_cover_match(&PostfitPi(), threshold, d_offsets(), G, d_members(), M, d_dsize(), d_tbest(),
                                      d_tover(), d_tsize(), d_dbest(), d_dover(), d_skipped(),
                                      overlap ? d_dense() : nullptr, d_ws(), ws_bytes, queue_.stream());
     if (rc != AMMSB_OK)
@@ -528,7 +542,7 @@ void Learner::CoverNMI(const std::vector<uint64_t>& offsets, const std::vector<u
         // (the host vectors are pageable: a write has returned when the device holds the data)
         d_offsets.Write(queue_, Gs + 1, rebased.data());
         d_members.Write(queue_, Ms, members.data() + offsets[g0]);
-        rc = ammsb_cover_match(&pi_->Get(), threshold, d_offsets(), Gs, d_members(), Ms, d_dsize(), d_tbest(), d_tover(),
+        rc = ammsb_cover_match(&PostfitPi(), threshold, d_offsets(), Gs, d_members(), Ms, d_dsize(), d_tbest(), d_tover(),
                                d_ts(), d_dbest(), d_dover(), d_skipped(), d_dense(), d_ws(), ws_bytes, queue_.stream());
         if (rc != AMMSB_OK) throw PostfitError("ammsb_cover_match", rc, ammsb_cover_last_error());
       } else {  // (the cover match launches nothing for communities without members: their overlap is 0)
@@ -667,7 +681,7 @@ void Learner::CoverOmega(const std::vector<uint64_t>& offsets, const std::vector
     Zero("CoverOmega", d_tbits(), std::max<uint64_t>(n * WT, 1) * sizeof(uint32_t), stream);
     Zero("CoverOmega", d_tcount(), n * sizeof(uint32_t), stream);
     Zero("CoverOmega", d_tally(), 2 * sizeof(uint64_t), stream);
-    int rc = ammsb_omega_detected_bits(&pi_->Get(), threshold, d_nodes(), n, d_dbits(), d_dcount(), stream);
+    int rc = ammsb_omega_detected_bits(&PostfitPi(), threshold, d_nodes(), n, d_dbits(), d_dcount(), stream);
     if (rc != AMMSB_OK) throw PostfitError("ammsb_omega_detected_bits", rc, ammsb_omega_last_error());
     rc = ammsb_omega_truth_bits(d_offsets(), G, d_members(), M, N, d_position(), n, d_tbits(), d_tcount(), d_tally(),
                                 d_tally() + 1, stream);
@@ -755,7 +769,7 @@ void Learner::CommunityOverlap(Float threshold, std::vector<uint32_t>* overlap, 
   queue_.Finish();
   const uint64_t K = pi_->Cols();
   clcuda::Buffer<uint32_t> d_overlap(queue_.GetContext(), K * K);
-  OverlapOnDevice(&pi_->Get(), threshold, max_bytes, &d_overlap, queue_.GetContext(), queue_.stream());
+  OverlapOnDevice(&PostfitPi(), threshold, max_bytes, &d_overlap, queue_.GetContext(), queue_.stream());
   overlap->resize(K * K);
   d_overlap.Read(queue_, K * K, overlap->data());
   queue_.Finish();
@@ -773,7 +787,7 @@ void Learner::RelatedCommunities(Float threshold, uint32_t top, const std::strin
   const clcuda::Context context = queue_.GetContext();
   clcuda::Buffer<uint32_t> d_overlap(context, K * K), d_shared(context, K * top);
   clcuda::Buffer<int32_t> d_partner(context, K * top);
-  OverlapOnDevice(&pi_->Get(), threshold, max_bytes, &d_overlap, context, queue_.stream());
+  OverlapOnDevice(&PostfitPi(), threshold, max_bytes, &d_overlap, context, queue_.stream());
   const int rc = ammsb_relate_top(d_overlap(), static_cast<uint32_t>(K), measure, top, min_overlap, d_partner(), d_shared(),
                                   queue_.stream());
   if (rc != AMMSB_OK) throw PostfitError("ammsb_relate_top", rc, ammsb_relate_last_error());
@@ -845,7 +859,7 @@ void Learner::CommunityLinks(Float threshold, std::vector<uint64_t>* links) {
   const uint64_t K = pi_->Cols();
   const clcuda::Context context = queue_.GetContext();
   clcuda::Buffer<uint64_t> d_links(context, K * K), d_counts(context, 2);
-  LinksOnDevice(&pi_->Get(), threshold, SortedTrainingLinks(cfg_), &d_links, &d_counts, context, queue_);
+  LinksOnDevice(&PostfitPi(), threshold, SortedTrainingLinks(cfg_), &d_links, &d_counts, context, queue_);
   links->resize(K * K);
   d_links.Read(queue_, K * K, links->data());
   queue_.Finish();
@@ -864,8 +878,8 @@ void Learner::LinkedCommunities(Float threshold, uint32_t top, const std::string
   clcuda::Buffer<uint32_t> d_overlap(context, K * K), d_shared(context, K * top);
   clcuda::Buffer<uint64_t> d_links(context, K * K), d_counts(context, 2), d_plinks(context, K * top);
   clcuda::Buffer<int32_t> d_partner(context, K * top);
-  OverlapOnDevice(&pi_->Get(), threshold, max_bytes, &d_overlap, context, queue_.stream());
-  LinksOnDevice(&pi_->Get(), threshold, SortedTrainingLinks(cfg_), &d_links, &d_counts, context, queue_);
+  OverlapOnDevice(&PostfitPi(), threshold, max_bytes, &d_overlap, context, queue_.stream());
+  LinksOnDevice(&PostfitPi(), threshold, SortedTrainingLinks(cfg_), &d_links, &d_counts, context, queue_);
   const int rc = ammsb_connect_top(d_links(), d_overlap(), static_cast<uint32_t>(K), measure, top, min_links, d_partner(),
                                    d_plinks(), d_shared(), queue_.stream());
   if (rc != AMMSB_OK) throw PostfitError("ammsb_connect_top", rc, ammsb_connect_last_error());
@@ -957,7 +971,7 @@ void Learner::Modularity(Float threshold, const std::vector<Edge>* edges, Modula
     clcuda::Buffer<Edge> d_edges(context, queue_, edges->begin(), edges->end());
     Zero("Modularity", d_sums(), (4 * K + 2) * sizeof(uint64_t), stream);
     Zero("Modularity", d_degree(), N * sizeof(uint32_t), stream);
-    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &PostfitPi(), threshold, context, stream);
     int rc = ammsb_modularity_edges(d_mask(), N, static_cast<uint32_t>(K), d_edges(), edges->size(), d_degree(), d_sums(),
                                 d_sums() + 4 * K, stream);
     if (rc == AMMSB_OK)
@@ -1093,7 +1107,7 @@ void Learner::NodeRoles(Float threshold, const std::vector<Edge>* edges, uint32_
     clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
     clcuda::Buffer<Vertex> d_targets(context, queue_, targets.begin(), targets.end());
     Zero("NodeRoles", d_sums(), (3 * K + 2) * sizeof(uint64_t), stream);
-    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &PostfitPi(), threshold, context, stream);
     int rc = ammsb_roles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N,
                            among == "own" ? AMMSB_ROLES_OWN : AMMSB_ROLES_ALL, top, min_count, d_node(), d_node() + N,
                            d_node() + 2 * N, d_node() + 3 * N, d_wide(), d_wide() + N, reinterpret_cast<int32_t*>(d_slots()),
@@ -1250,7 +1264,7 @@ void Learner::Triangles(Float threshold, const std::vector<Edge>* edges, Triangl
     clcuda::Buffer<uint64_t> d_offsets(context, queue_, offsets.begin(), offsets.end());
     clcuda::Buffer<Vertex> d_targets(context, queue_, targets.begin(), targets.end());
     Zero("Triangles", d_sums(), (5 * K + 4) * sizeof(uint64_t), stream);
-    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &PostfitPi(), threshold, context, stream);
     int rc = ammsb_triangles_nodes(d_mask(), N, static_cast<uint32_t>(K), d_offsets(), d_targets(), 0, N, d_node(), d_node() + N,
                                d_node() + 2 * N, d_sums(), d_sums() + K, d_sums() + 2 * K, stream);
     if (rc != AMMSB_OK) throw PostfitError("ammsb_triangles_nodes", rc, ammsb_triangles_last_error());
@@ -1338,7 +1352,7 @@ void Learner::CommunityComponents(Float threshold, ComponentsResult* result, con
     hipStream_t stream = static_cast<hipStream_t>(queue_.stream());
     const clcuda::Context context = queue_.GetContext();
     clcuda::Buffer<uint32_t> d_node(context, 2 * N);  // own, then stray
-    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &PostfitPi(), threshold, context, stream);
     int rc = ammsb_components_own(d_mask(), N, cols, d_node(), stream);
     if (rc != AMMSB_OK) throw PostfitError("ammsb_components_own", rc, ammsb_components_last_error());
     // base: a host prefix sum over the downloaded own
@@ -1470,7 +1484,7 @@ void Learner::CommunityCores(Float threshold, CoresResult* result, const std::ve
     if (targets.empty()) targets.push_back(0);  // (a buffer needs a byte; no offset reaches it)
     clcuda::Buffer<uint32_t> d_node4(context, 4 * N);  // own best_core best_comm in_nucleus
     uint32_t* const d_node = d_node4();
-    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &pi_->Get(), threshold, context, stream);
+    const clcuda::Buffer<uint64_t> d_mask = MembershipMask("ammsb_connect_mask", &PostfitPi(), threshold, context, stream);
     int rc = ammsb_components_own(d_mask(), N, cols, d_node, stream);
     if (rc != AMMSB_OK) throw PostfitError("ammsb_components_own", rc, ammsb_components_last_error());
     std::vector<uint32_t> own(N);

@@ -259,6 +259,7 @@ class Learner(PostFit):
         self.ref_sampler = None
         self.loop = None
         self._loop_dirty = False
+        self._average = None  # ops.ChainAverage while StartAverage() is in force
         if cfg.device_sampling:
             off, tgt = dataset.training_csr()  # the host Graph's adjacency order (Graph::ExportCSR)
             # held-out links of a vertex are invalid non-link partners too (sample.cc:283-285)
@@ -781,6 +782,10 @@ class Learner(PostFit):
                 rec = {"n_nodes": n_nodes, "n_edges": n_edges, "marks": []}
                 self.shard_trace.append(rec)
             self._mark(rec, "begin")
+            avg = self._average
+            if avg is not None and avg.n:
+                # the rows this iteration overwrites: their mean is brought up to the samples so far first
+                avg.rows(self.pi, avg.n, nodes=s.dev_nodes, count=n_nodes)
             self._phi_sharded(s, n_nodes, rec)
             self._mark(rec, "phi_end")
             beta = self.betaUpdater
@@ -809,6 +814,9 @@ class Learner(PostFit):
                 self._mark(rec, "grads_local")
             self._mark(rec, "grads_reduced")
             beta.update_theta(weight, total)
+            if avg is not None:
+                avg.n += 1
+                avg.vector(self.beta, avg.n)
             self._mark(rec, "end")
 
             ops.record_event(s.consumed)
@@ -1014,6 +1022,7 @@ class Learner(PostFit):
             f.set_result(float(np.float32(props[5])))
             self.futures[self.phase] = f
         self.ops.synchronize()
+        self.StopAverage()  # the checkpoint does not carry it
         return True
 
     def drain(self):
@@ -1027,6 +1036,40 @@ class Learner(PostFit):
             self._loop_dirty = False
         if self.dev_sampler is not None:
             self.dev_sampler.check()  # a mini-batch that came up short is an error, never a silent duplicate
+
+    # ------------------------------------------------------------------ the chain average (include/ammsb_average.h)
+
+    def StartAverage(self):
+        """From now on keep the mean of (pi, beta) over the iterations: sample t is the state after the t-th iteration
+        from here.  Costs a second pi in device memory and, per iteration, one flush of the mini-batch rows before they
+        are overwritten plus a 2K-element fold of beta.  Restarting sets the count back to 0.  Only the eager loop on one
+        rank is covered."""
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: the chain average has no CPU path")
+        if self.loop is not None:
+            raise AmmsbError("the chain average is kept by the eager loop: construct the learner with graph_launch=False")
+        if self.sharded:
+            raise AmmsbError("the chain average covers one rank (world_size 1, no force_exchange)")
+        if self._average is None:
+            self._average = self.ops.ChainAverage(self.ctx, self.pi, self.beta)
+        else:
+            self._average.reset()
+
+    def StopAverage(self):
+        """Drop the average and its buffers; views made by Averaged() stop working."""
+        self._average = None
+
+    @property
+    def AverageSamples(self):
+        """iterations averaged so far (0: no average, or none yet)"""
+        return self._average.n if self._average is not None else 0
+
+    def Averaged(self):
+        """-> AveragedModel: every post-fit analysis of this learner, over the mean of (pi, beta) instead of the last
+        draw.  Raises before the first averaged iteration."""
+        if self._average is None or self._average.n == 0:
+            raise AmmsbError("Averaged(): no sample yet (StartAverage(), then Run)")
+        return AveragedModel(self)
 
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)
@@ -1044,3 +1087,29 @@ class Learner(PostFit):
         if self.ref_sampler is not None:
             self.ref_sampler.close()  # its device workspace and pinned result page
             self.ref_sampler = None
+
+
+class AveragedModel(PostFit):
+    """The post-fit analyses over the chain average of a Learner: pi is the mean matrix, beta the mean rounded to float32,
+    everything else the learner's.  drain() drains the learner and flushes every row of the mean (row slabs; nothing is
+    launched when nothing ran since the last flush), so a view stays valid across further Run() calls and always answers
+    for all samples so far.  No CPU path."""
+
+    def __init__(self, learner):
+        L = learner
+        self.learner, self._avg = L, L._average
+        self.ops, self.ctx, self.cfg, self.params, self.dataset = L.ops, L.ctx, L.cfg, L.params, L.dataset
+        self.trainingSet, self.heldoutSet, self.heldoutEdges = L.trainingSet, L.heldoutSet, L.heldoutEdges
+        self.pi, self.beta = self._avg.mean, self._avg.beta32
+        self.drain()
+
+    @property
+    def samples(self):
+        return self._avg.n
+
+    def drain(self):
+        L = self.learner
+        if L._average is not self._avg:
+            raise AmmsbError("this view's average was stopped (StopAverage, Parse or a new learner state)")
+        L.drain()
+        self._avg.flush(L.pi)

@@ -1865,6 +1865,70 @@ class CommunityCores:
         return self.co.last_kernel_name()
 
 
+class ChainAverage:
+    """The running mean of (pi, beta) over the iterations since it was started (include/ammsb_average.h).  Owns a second
+    matrix of pi's geometry (left uninitialised: a row's first flush does not read it), last [N], beta's binary64 mean
+    and its binary32 rounding.  n counts the samples; the owner of the loop calls rows() with the mini-batch nodes and the
+    n BEFORE an iteration, then bumps n and calls vector() after it.  flush() brings every row to n before a read."""
+
+    FLUSH_SLAB_BYTES = 256 << 20  # most bytes of pi one flush launch walks
+
+    def __init__(self, ctx, pi, beta):
+        from . import _average
+        self.ctx = ctx
+        self.av = _average
+        self.lib = _average.load()
+        self.mean = RowPartitionedMatrix(ctx, pi.rows, pi.cols, pi.rows_in_block)
+        self.last = ctx.zeros((pi.rows,), torch.int32)
+        self.beta64 = ctx.empty((int(beta.numel()),), torch.float64)
+        self.beta32 = ctx.empty((int(beta.numel()),), torch.float32)
+        self.n = 0
+        self.flushed = 0   # the n every row and beta32 were last brought to
+
+    def reset(self):
+        self.last.zero_()
+        self.n = self.flushed = 0
+
+    def rows(self, pi, n, nodes=None, count=None, first=0):
+        """flush the rows nodes[:count] (a contiguous int32 device tensor of uint32 ids), or first .. first + count, to n"""
+        if nodes is not None:
+            if nodes.dtype != torch.int32 or not nodes.is_contiguous():
+                raise AmmsbError("chain average: nodes must be a contiguous int32 (uint32 bits) device tensor")
+            count = int(nodes.numel()) if count is None else int(count)
+            if count > nodes.numel():
+                raise AmmsbError("chain average: count %d past the %d listed nodes" % (count, nodes.numel()))
+        else:
+            count = pi.rows - int(first) if count is None else int(count)
+        self.av.check(self.lib.ammsb_average_rows(C.byref(pi.desc), C.byref(self.mean.desc), _ptr(self.last), _ptr(nodes),
+                                                  int(first), count, int(n), _stream()))
+
+    def vector(self, x, n):
+        """fold the float32 vector x (beta) into the binary64 mean as sample n"""
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != self.beta64.numel():
+            raise AmmsbError("chain average: not the learner's beta")
+        self.av.check(self.lib.ammsb_average_vector(_ptr(x), _ptr(self.beta64), int(x.numel()), int(n), _stream()))
+
+    def round(self):
+        """-> beta's mean rounded to float32 (the tensor the views hold)"""
+        self.av.check(self.lib.ammsb_average_round(_ptr(self.beta64), _ptr(self.beta32), int(self.beta64.numel()), _stream()))
+        return self.beta32
+
+    def flush(self, pi):
+        """every row of mean and beta32 up to date with n; nothing is launched when nothing ran since the last flush"""
+        if self.n == 0:
+            raise AmmsbError("chain average: no sample yet")
+        if self.flushed == self.n:
+            return
+        slab = max(1, self.FLUSH_SLAB_BYTES // (4 * pi.cols))
+        for lo in range(0, pi.rows, slab):
+            self.rows(pi, self.n, first=lo, count=min(slab, pi.rows - lo))
+        self.round()
+        self.flushed = self.n
+
+    def kernel_name(self):
+        return self.av.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
