@@ -1,12 +1,20 @@
 """Runs the rows of one environment group of kernel_forms.ROWS against the oracle, in this (child) process.
 
     python kernel_forms_child.py GROUP REF_IN|- [REF_OUT]
+    python kernel_forms_child.py GROUP edges [FIRST LAST [REF_IN]]
+    python kernel_forms_child.py 0 edge-refs REF_OUT
 
 GROUP indexes kernel_forms.groups(); the caller sets that group's environment.  REF_IN: an .npz of default-form
 gradients (keyed by ref_key) that the gradient rows of this group must equal bit for bit ("-": none).  REF_OUT: where
 to save, computed with this process's dispatch, the gradients of every gradient row of the OTHER groups that keeps the
 slot count (the default group writes it).  Prints "row ok <index>" per row and "group ok" at the end.
+
+`edges`: the phi, grads and fused rows of the group (those with FIRST <= index in ROWS <= LAST) on the inputs of
+division_edges.py, which put every form on both sides of its exact-division branch; every comparison bit for bit
+(both-NaN allowed).  REF_IN: default-form gradients of the same inputs, written by `0 edge-refs REF_OUT` in the default
+environment, for the gradient rows of another group.  Prints "edge ok <index>" per row and "group ok".
 """
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -19,6 +27,7 @@ for p in (ROOT, HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import division_edges as de  # noqa: E402
 import kernel_forms as kf  # noqa: E402
 
 SLOT = {k: i for i, k in enumerate(("update_phi", "update_pi", "beta_grads", "perplexity", "update_phi_small",
@@ -46,6 +55,71 @@ def check_names(ctx, row, what):
     got = raw_names(ctx)
     for slot, want in row.kernel.items():
         assert kf.normalize(got[slot]) == want, (what, slot, got[slot], want, row)
+
+
+# ---- the edges mode: what a row runs (shared with test_division_edges_host.py, which checks the coverage on the CPU)
+EDGE_NODES = 96
+EDGE_DEG = 16  # both directions: about 32 graph neighbours per node, so half of any neighbour row can be links
+
+
+def edge_deg(row):
+    """graph density of a row's state: for the gradient a graph in which the node of largest degree has well over a
+    hundred links (about 300 edges in the list), as far as N leaves as many non-neighbours"""
+    return EDGE_DEG if row.op == "phi" else grad_deg(row.shape[0])
+
+
+def grad_deg(N):
+    return min(64, N // 4)
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return bool(((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def edge_nodes(row):
+    """mini-batch nodes of a phi row in the edges mode: its own, but 96 for a row of more than 512 whose form does not
+    depend on the count (the small-launch, persistent-grid and stream rows keep theirs)"""
+    nodes = row.shape[3]
+    keeps = row.flags == "small" or any(k in ("AMMSB_PHI_PERSIST", "AMMSB_PHI_STREAM") for k, _ in row.env)
+    return nodes if nodes <= 512 or keeps else EDGE_NODES
+
+
+def edge_state_shape(row):
+    """(N, K, n, mini-batch nodes) of the Problem a row's edges run builds"""
+    N, K, n = row.shape[:3]
+    return (N, K, n, edge_nodes(row) if row.op == "phi" else 16)
+
+
+def phi_case(st, case, eps):
+    """applies `case` to the state and asserts its coverage conditions; returns (classes, tally)"""
+    de.apply_case(st, case, eps)
+    cls = de.classify_phi(st, eps)
+    return cls, de.check_phi_coverage(case, cls)
+
+
+def grad_case(orc, p_orc, st, case, eps, fused, wg):
+    """The pi state of `case`, its node-strategy edge list, coverage asserted.  fused: phi_vec rows are planted so that
+    update_pi reproduces (up to its normalisation) the edited pi rows of u and the partners; the classes are those of
+    the pi rows AFTER the oracle's update_pi, which is what the gradient of the fused launch reads."""
+    rng = np.random.default_rng(17)
+    {"trained": de.trained, "denormal": de.denormal}.get(case, lambda s, r: de.mixed(s, r, eps))(st, rng)
+    u, partners, links = de.grad_edges(st, rng, eps)
+    c = {"u": u, "partners": partners, "links": links,
+         "edges": ((np.minimum(u, partners).astype(np.uint64) << np.uint64(32)) | np.maximum(u, partners).astype(np.uint64))}
+    c["pi"] = st.pi_h
+    if fused:
+        c["nodes"] = np.concatenate([[u], partners]).astype(np.uint32)
+        with np.errstate(all="ignore"):
+            c["phi_vec"] = (st.pi_h[c["nodes"]] * st.phi_sum_h[c["nodes"], None]).astype(np.float32)
+        c["pi"], c["phi_sum"] = st.pi_h.copy(), st.phi_sum_h.copy()
+        orc.update_pi(p_orc, c["pi"].reshape(-1), c["phi_sum"], c["phi_vec"].reshape(-1), c["nodes"], wg, 1)
+        after = de.State()
+        after.pi_h, after.beta_h = c["pi"], st.beta_h
+        st = after
+    c["fast"] = de.classify_grads(st, eps, u, partners, links)
+    c["count"] = de.check_grad_coverage(case, links, c["fast"])
+    return c
 
 
 class Runner:
@@ -154,18 +228,21 @@ class Runner:
         pr.ctx.close()
         return g
 
-    def summed_in_order(self, pr, mbe, wg, P):
+    def summed_in_order(self, pr, mbe, wg, P, pi_h=None):
         """the gradient as P slots sum it (test_gpu_parity.py::test_beta_gradient_association_order_is_fixed): slot s
-        adds edges s, s + P, ...; sum_partials8_kernel's row-lane r adds slots r, r + 128, ..., then a halving tree"""
-        terms = np.stack([self.orc.beta_grads(pr.p_orc, pr.theta_h, pr.beta_h, pr.pi_h.reshape(-1), pr.oset, mbe[i:i + 1],
+        adds edges s, s + P, ...; sum_partials8_kernel's row-lane r adds slots r, r + 128, ..., then a halving tree
+        (sum_partials_kernel, K % 4 != 0: 16 row-lanes)"""
+        pi_h = pr.pi_h if pi_h is None else pi_h
+        terms = np.stack([self.orc.beta_grads(pr.p_orc, pr.theta_h, pr.beta_h, pi_h.reshape(-1), pr.oset, mbe[i:i + 1],
                                               wg, 1, order=0) for i in range(mbe.size)]).astype(np.float32)
         rows = np.zeros((P, terms.shape[1]), dtype=np.float32)
         for e in range(mbe.size):
             rows[e % P] = rows[e % P] + terms[e]
-        lanes = np.zeros((128, terms.shape[1]), dtype=np.float32)
+        R = 128 if pr.K % 4 == 0 else 16
+        lanes = np.zeros((R, terms.shape[1]), dtype=np.float32)
         for p in range(P):
-            lanes[p % 128] = lanes[p % 128] + rows[p]
-        half = 64
+            lanes[p % R] = lanes[p % R] + rows[p]
+        half = R // 2
         while half > 0:
             lanes[:half] = lanes[:half] + lanes[half:2 * half]
             half //= 2
@@ -281,7 +358,159 @@ class Runner:
             assert np.array_equal(smp.rand.host(), seeds), ("streams", row)
         ctx.close()
 
-    def run(self, row, refs):
+    # ---- the edges mode (division_edges.py): one update_phi (noise on) + update_pi per case, bit for bit
+    def _edge_problem(self, row):
+        N, K, n, nodes = edge_state_shape(row)
+        pr = self.problem(row, n_nodes=nodes, deg=edge_deg(row))
+        if N * K <= 1 << 20:  # the host tests build the same state without a device
+            hs = de.host_state(self.orc, N, K, n, nodes, deg=edge_deg(row))
+            for f in ("pi_h", "phi_sum_h", "beta_h", "nb_h", "nodes_h", "edges"):
+                assert np.array_equal(getattr(hs, f), getattr(pr, f)), ("host_state differs from Problem", f)
+        return pr
+
+    def _upload(self, pr):
+        pr.pi.load(pr.pi_h)
+        pr.phi_sum.copy_(pr.ctx.from_numpy(pr.phi_sum_h))
+        pr.beta.copy_(pr.ctx.from_numpy(pr.beta_h))
+        pr.nb.copy_(pr.ctx.from_numpy(pr.nb_h))
+
+    def phi_edges(self, row):
+        orc, hip = self.orc, self.hip
+        N, K, n, _, wg = row.shape
+        nodes = edge_nodes(row)
+        if any(k == "AMMSB_PHI_PERSIST" for k, _ in row.env):
+            assert nodes > 32 * self.torch.cuda.get_device_properties(0).multi_processor_count, row
+        pr = self._edge_problem(row)
+        saved = de.Saved(pr)
+        eps = pr.p_orc.epsilon
+        upd = hip.PhiUpdater(pr.ctx, pr.beta, pr.pi, pr.phi_sum, pr.dset, nodes, (42, 43), wg,
+                             streaming_only=row.flags == "streaming")
+        seeds = orc.rng_init(nodes * wg, 42, 43)
+        for case in de.CASES:
+            saved.restore(pr)
+            cls, tally = phi_case(pr, case, eps)
+            flags = pr.oset.has(orc.make_edge(pr.nodes_h[:, None], pr.nb_h).reshape(-1)).reshape(pr.nb_h.shape)
+            assert np.array_equal(flags, de.link_flags(pr)), ("link flags", case, row)
+            self._upload(pr)
+            upd.count_calls = 1
+            upd.update_phi(pr.nodes, pr.nb, nodes)
+            pr.sync()
+            want = orc.update_phi(pr.p_orc, pr.beta_h, pr.pi_h.reshape(-1), pr.phi_sum_h, pr.oset, pr.nodes_h,
+                                  pr.nb_h.reshape(-1), 1, seeds, wg, 1, True)
+            got = upd.phi_vec.cpu().numpy()[:nodes]
+            if not same_bits(got, want):
+                bad = np.argwhere((bits(got) != bits(want)) & ~(np.isnan(got) & np.isnan(want)))
+                raise AssertionError(("phi_vec", case, row, len(bad), bad[:5].tolist(),
+                                      [(cls.fast[i].sum(), cls.slow[i].sum()) for i in np.unique(bad[:5, 0])]))
+            assert np.array_equal(upd.rand.host(), seeds), ("streams", case, row)
+            pi_h, phi_sum_h = pr.pi_h.copy(), pr.phi_sum_h.copy()
+            orc.update_pi(pr.p_orc, pi_h.reshape(-1), phi_sum_h, want.reshape(-1), pr.nodes_h, wg, 1)
+            upd.update_pi(pr.nodes, nodes)
+            pr.sync()
+            check_names(pr.ctx, row, case)
+            finite = np.ones(N, dtype=bool)
+            finite[pr.nodes_h[~np.isfinite(want).all(1)]] = False  # (where the oracle's phi_vec is finite)
+            if N > 10000:
+                keep = np.zeros(N, dtype=bool)
+                keep[pr.nodes_h] = True
+                finite &= keep
+            rows = np.flatnonzero(finite)
+            assert same_bits(pr.pi.host()[rows], pi_h[rows]), ("pi", case, row)
+            assert same_bits(pr.phi_sum.cpu().numpy()[rows], phi_sum_h[rows]), ("phi_sum", case, row)
+            print("  %s: fast %.3f slow %.3f undecided %.3f" % (case, tally["fast"], tally["slow"], tally["undecided"]), flush=True)
+        pr.ctx.close()
+
+    @contextlib.contextmanager
+    def _slots(self):
+        """AMMSB_BETA_SLOTS (read at every call) at the slot count the edge lists are laid out for"""
+        old = os.environ.get("AMMSB_BETA_SLOTS")
+        os.environ["AMMSB_BETA_SLOTS"] = str(de.BETA_SLOTS)
+        try:
+            yield
+        finally:
+            if old is None:
+                del os.environ["AMMSB_BETA_SLOTS"]
+            else:
+                os.environ["AMMSB_BETA_SLOTS"] = old
+
+    def grads_edges(self, row, refs, out=None):
+        """gradient rows: trained / denormal / mixed pi, the node-strategy list, 64 slots; against summed_in_order bit for
+        bit, and against the default form's gradient (refs) where the row keeps the slot count.  out: save, do not check."""
+        orc, hip = self.orc, self.hip
+        N, K, _, _, wg = row.shape
+        pr = self._edge_problem(row)
+        saved = de.Saved(pr)
+        eps = pr.p_orc.epsilon
+        for case in de.GRAD_CASES:
+            saved.restore(pr)
+            c = grad_case(orc, pr.p_orc, pr, case, eps, False, wg)
+            mbe = c["edges"]
+            assert np.array_equal(pr.oset.has(mbe), c["links"]), ("link flags", case, row)
+            self._upload(pr)
+            upd = hip.BetaUpdater(pr.ctx, pr.theta, pr.beta, pr.pi, pr.dset, (44, 45), wg)
+            upd.count_calls += 1
+            with self._slots():
+                g = upd.calculate_grads(pr.ctx.from_numpy(mbe), mbe.size).cpu().numpy().copy()
+            key = "%s_%s" % (ref_key(row), case)
+            if out is not None:
+                out[key] = g
+                continue
+            check_names(pr.ctx, row, case)
+            want = self.summed_in_order(pr, mbe, wg, de.BETA_SLOTS)
+            assert same_bits(g, want), ("grads: not the oracle's terms in the order of 64 slots", case, c["count"], row)
+            if refs is not None and keeps_slots(row):
+                assert same_bits(g, refs[key]), ("grads differ from the default form", case, row)
+            print("  %s: %d edges %s" % (case, mbe.size, c["count"]), flush=True)
+        pr.ctx.close()
+
+    def fused_edges(self, row):
+        orc, hip, torch = self.orc, self.hip, self.torch
+        N, K, n, _, wg = row.shape
+        pr = self._edge_problem(row)
+        saved = de.Saved(pr)
+        eps = pr.p_orc.epsilon
+        phi = hip.PhiUpdater(pr.ctx, pr.beta, pr.pi, pr.phi_sum, pr.dset, de.MAX_EDGES + 1, (42, 43), wg, streaming_only=True)
+        bu = hip.BetaUpdater(pr.ctx, pr.theta, pr.beta, pr.pi, pr.dset, (44, 45), wg)
+        for case in de.GRAD_CASES:
+            saved.restore(pr)
+            c = grad_case(orc, pr.p_orc, pr, case, eps, True, wg)
+            edges, nodes_h = c["edges"], c["nodes"]
+            m = nodes_h.size
+            assert np.array_equal(pr.oset.has(edges), c["links"]), ("link flags", case, row)
+            d_edges, d_nodes = pr.ctx.from_numpy(edges), pr.ctx.from_numpy(nodes_h)
+            phi.phi_vec[:m].copy_(pr.ctx.from_numpy(c["phi_vec"]))
+            want = self.summed_in_order(pr, edges, wg, de.BETA_SLOTS, pi_h=c["pi"])
+            rows = np.unique(nodes_h)
+            for form in ("separate", "fused"):
+                self._upload(pr)
+                bu.count_calls = 1
+                with self._slots():
+                    if form == "separate":
+                        phi.update_pi(d_nodes, m)
+                        g = bu.calculate_grads(d_edges, edges.size)
+                    else:
+                        g = bu.update_pi_and_grads(phi, d_nodes, d_edges, edges.size)
+                    torch.cuda.synchronize()
+                if form == "fused":
+                    check_names(pr.ctx, row, case)
+                assert same_bits(pr.pi.host()[rows], c["pi"][rows]), ("pi rows", form, case, row)
+                assert same_bits(pr.phi_sum.cpu().numpy()[rows], c["phi_sum"][rows]), ("phi_sum", form, case, row)
+                assert same_bits(g.cpu().numpy(), want), ("grads", form, case, c["count"], row)
+            print("  %s: %d edges %s" % (case, edges.size, c["count"]), flush=True)
+        pr.ctx.close()
+
+    def run_edges(self, row, refs):
+        with self._phi_forms(row):
+            if row.op == "phi":
+                self.phi_edges(row)
+            elif row.op == "grads":
+                self.grads_edges(row, refs)
+            elif row.op == "fused":
+                self.fused_edges(row)
+
+    @contextlib.contextmanager
+    def _phi_forms(self, row):
+        """the row's ammsb_debug_phi_forms switch, reset afterwards"""
         phi_forms = row.debug.get("phi_forms")
         lib = None
         if phi_forms is not None:
@@ -289,6 +518,13 @@ class Runner:
             lib = _capi.load()
             lib.ammsb_debug_phi_forms(*phi_forms)
         try:
+            yield
+        finally:
+            if lib is not None:
+                lib.ammsb_debug_phi_forms(-1, -1, -1)
+
+    def run(self, row, refs):
+        with self._phi_forms(row):
             if row.op == "phi":
                 self.phi(row)
             elif row.op == "grads":
@@ -301,9 +537,6 @@ class Runner:
                 self.nbr(row)
             else:
                 raise ValueError(row.op)
-        finally:
-            if lib is not None:
-                lib.ammsb_debug_phi_forms(-1, -1, -1)
 
 
 def main():
@@ -316,6 +549,25 @@ def main():
     lib = _capi.load()
     lib.ammsb_debug_phi_forms.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ammsb_debug_beta_pi_nt.argtypes = [C.c_int]
+    if len(sys.argv) > 2 and sys.argv[2] == "edge-refs":
+        assert env == ()
+        out = {}
+        for e, others in kf.groups()[1:]:
+            for _, row in others:
+                if row.op == "grads" and keeps_slots(row) and "%s_%s" % (ref_key(row), de.GRAD_CASES[0]) not in out:
+                    r.grads_edges(row._replace(kernel={}), None, out)
+        np.savez(sys.argv[3], **out)
+        print("group ok", flush=True)
+        return
+    if len(sys.argv) > 2 and sys.argv[2] == "edges":
+        first, last = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (0, len(kf.ROWS))
+        refs = dict(np.load(sys.argv[5])) if len(sys.argv) > 5 else None
+        for i, row in rows:
+            if first <= i <= last and row.op in ("phi", "grads", "fused"):
+                r.run_edges(row, refs)
+                print("edge ok %d" % i, flush=True)
+        print("group ok", flush=True)
+        return
     refs = None
     if len(sys.argv) > 2 and sys.argv[2] != "-":
         refs = dict(np.load(sys.argv[2]))
