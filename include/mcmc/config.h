@@ -125,6 +125,10 @@ struct Config {
 
 std::ostream& operator<<(std::ostream& out, const Config& cfg);
 
+// Every field of cfg; the sets and graphs, which a Config owns, as copies of their own (Learner::Reduce: a learner at
+// another K needs a Config that outlives it).
+std::unique_ptr<Config> CloneConfig(const Config& cfg);
+
 // The -D constants of MakeCompileFlags (config.cc:66-83) as the POD the C ABI takes, including the
 // "%e" round trip every float goes through there.
 ammsb_params MakeKernelParams(const Config& cfg);

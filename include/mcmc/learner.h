@@ -53,6 +53,18 @@ class Learner {
   // std::runtime_error while no sample exists).  Off by default.
   void ReadAverage(bool on) { read_average_ = on; }
 
+  // Fewer communities (include/ammsb_reduce.h; not in the reference API).  map[K]: map[k] = j sends community k to the new
+  // community j in [0, K'), -1 drops it; every new community needs a source.  -> a new learner over the same data (it owns a
+  // copy of the Config with K = K', alpha as this Config holds it) and the same queue, whose pi, phi_sum and theta are this
+  // learner's under the plan and whose beta follows from theta; stepCount, the times, the mini-batch edges and the two
+  // updaters' step counters are carried over, so the step size continues.  Its RNG streams, sampler state (the pending
+  // mini-batch included) and perplexity running mean are its own fresh ones.  This learner is only drained.  Both pi
+  // matrices are alive at once.  Throws std::invalid_argument on a bad map (the id is named) and when the run is sharded.
+  std::unique_ptr<Learner> Reduce(const std::vector<int32_t>& map);
+  uint64_t ReducedFromK() const { return reduced_from_K_; }  // 0: not made by Reduce
+  uint64_t EmptiedRows() const { return emptied_rows_; }     // rows the plan left without mass (set uniform)
+  std::vector<Float> GetPhiSum();
+
   // Reading the model out (include/ammsb_readout.h; not in the reference API).  Per node its `top` (1..16) strongest
   // communities, value descending and equal values by community ascending: ids / weights are [N, top], a slot below
   // `threshold` (>= 0) or past K holds 0xFFFFFFFF / 0; count[a] = communities >= threshold, not capped at top;
@@ -372,6 +384,8 @@ class Learner {
   const Float* PostfitBeta();
   void FlushAverage();  // every row of mean_pi_ and mean_beta_ up to avg_n_; nothing is launched when nothing ran since
 
+  std::unique_ptr<Config> owned_cfg_;  // a learner made by Reduce(): what cfg_ refers to (first member: destroyed last)
+  uint64_t reduced_from_K_ = 0, emptied_rows_ = 0;
   const Config& cfg_;
   clcuda::Queue queue_;
   clcuda::Buffer<Float> beta_;
@@ -447,6 +461,13 @@ class Learner {
 // learner.cc:47-75: the first training_ppx_ratio * |training| training edges, then links * (N(N-1)/2) / E random
 // pairs (u != v, MakeEdge(u, v) as drawn -- NOT canonicalised, as in the reference) that are in neither set.
 std::vector<Edge> MakeEdgesForTrainingPerplexity(const Config& cfg);
+
+// A plan (the map of Learner::Reduce) as text, byte for byte what mcmc-ammsb-gpu_amd/_reduce.py writes: `# K new_K dropped`,
+// then `j n k0 k1 ...` per new community (sources ascending) and `x k` per dropped one.  PlanSources validates a map and
+// returns its inverse CSR (std::invalid_argument names the offending id); ReadPlan throws it for a file that is no plan.
+void PlanSources(const std::vector<int32_t>& map, std::vector<uint32_t>* src_off, std::vector<uint32_t>* src);
+bool WritePlan(std::ostream* out, const std::vector<int32_t>& map);
+std::vector<int32_t> ReadPlan(std::istream* in);
 
 }  // namespace mcmc
 

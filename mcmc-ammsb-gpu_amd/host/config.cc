@@ -111,6 +111,64 @@ ammsb_params MakeKernelParams(const Config& cfg) {
   return p;
 }
 
+std::unique_ptr<Config> CloneConfig(const Config& c) {
+  std::unique_ptr<Config> n(new Config);
+  n->heldout_ratio = c.heldout_ratio;
+  n->alpha = c.alpha;
+  n->a = c.a;
+  n->b = c.b;
+  n->c = c.c;
+  n->epsilon = c.epsilon;
+  n->eta0 = c.eta0;
+  n->eta1 = c.eta1;
+  n->K = c.K;
+  n->mini_batch_size = c.mini_batch_size;
+  n->num_node_sample = c.num_node_sample;
+  n->N = c.N;
+  n->E = c.E;
+  n->training_edges = c.training_edges;
+  n->heldout_edges = c.heldout_edges;
+  if (c.training) n->training.reset(new Set(*c.training));
+  if (c.heldout) n->heldout.reset(new Set(*c.heldout));
+  if (c.trainingGraph) n->trainingGraph.reset(new Graph(*c.trainingGraph));
+  if (c.heldoutGraph) n->heldoutGraph.reset(new Graph(*c.heldoutGraph));
+  n->ppx_wg_size = c.ppx_wg_size;
+  n->ppx_interval = c.ppx_interval;
+  n->neighbor_sampler_wg_size = c.neighbor_sampler_wg_size;
+  n->phi_wg_size = c.phi_wg_size;
+  n->beta_wg_size = c.beta_wg_size;
+  n->phi_seed = c.phi_seed;
+  n->beta_seed = c.beta_seed;
+  n->neighbor_seed = c.neighbor_seed;
+  n->phi_disable_noise = c.phi_disable_noise;
+  n->calc_train_ppx = c.calc_train_ppx;
+  n->training_ppx_ratio = c.training_ppx_ratio;
+  n->training_ppx_seed = c.training_ppx_seed;
+  n->strategy = c.strategy;
+  n->phi_mode = c.phi_mode;
+  n->phi_probs_shared = c.phi_probs_shared;
+  n->phi_grads_shared = c.phi_grads_shared;
+  n->phi_pi_shared = c.phi_pi_shared;
+  n->phi_vector_width = c.phi_vector_width;
+  n->sum_grads_vector_width = c.sum_grads_vector_width;
+  n->device_sampling = c.device_sampling;
+  n->sampling_stream = c.sampling_stream;
+  n->async_launch = c.async_launch;
+  n->graph_launch = c.graph_launch;
+  n->loop_timers = c.loop_timers;
+  n->exchange = c.exchange;
+  n->device_sampling_seed = c.device_sampling_seed;
+  n->device_sampling_host_seed = c.device_sampling_host_seed;
+  n->sample_seed[0] = c.sample_seed[0];
+  n->sample_seed[1] = c.sample_seed[1];
+  n->phi_chunks = c.phi_chunks;
+  n->phi_replicate = c.phi_replicate;
+  n->beta_shard_min_edges = c.beta_shard_min_edges;
+  n->beta_grads = c.beta_grads;
+  n->pi_placement_candidates = c.pi_placement_candidates;
+  return n;
+}
+
 std::ostream& operator<<(std::ostream& out, const Config& cfg) {  // config.cc:85-116
   out << "Config:\n"
       << "heldout ratio: " << cfg.heldout_ratio << "\n"

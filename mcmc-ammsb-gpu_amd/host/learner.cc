@@ -8,12 +8,14 @@
 #include "mcmc/serialize.h"
 #include "ammsb_refsample.h"
 #include "ammsb_average.h"
+#include "ammsb_reduce.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <iostream>
@@ -1105,6 +1107,149 @@ std::vector<Float> Learner::GetPiRow(Vertex v) {
   const uint32_t blk = v / pi_->RowsPerBlock();
   pi_->Blocks()[blk].Read(queue_, cfg_.K, row.data(), (size_t)(v % pi_->RowsPerBlock()) * cfg_.K);
   return row;
+}
+
+std::vector<Float> Learner::GetPhiSum() {
+  std::vector<Float> v(cfg_.N);
+  phi_.Read(queue_, v.size(), v.data());
+  return v;
+}
+
+// ---- fewer communities (include/ammsb_reduce.h)
+void PlanSources(const std::vector<int32_t>& map, std::vector<uint32_t>* src_off, std::vector<uint32_t>* src) {
+  const uint64_t K = map.size();
+  if (K == 0 || K > AMMSB_REDUCE_MAX_COLS)
+    throw std::invalid_argument("a plan covers 1..8192 communities, not " + std::to_string(K));
+  int64_t new_K = 0;
+  for (uint64_t k = 0; k < K; ++k) {
+    if (map[k] < -1 || map[k] >= static_cast<int64_t>(K))
+      throw std::invalid_argument("community " + std::to_string(k) + " is sent to " + std::to_string(map[k]) + ": outside -1.." +
+                                  std::to_string(K - 1));
+    new_K = std::max<int64_t>(new_K, static_cast<int64_t>(map[k]) + 1);
+  }
+  if (new_K == 0) throw std::invalid_argument("the plan drops every community (community 0 included): nothing would be left");
+  src_off->assign(new_K + 1, 0);
+  for (uint64_t k = 0; k < K; ++k)
+    if (map[k] >= 0) ++(*src_off)[map[k] + 1];
+  for (int64_t j = 0; j < new_K; ++j) {
+    if ((*src_off)[j + 1] == 0) throw std::invalid_argument("new community " + std::to_string(j) + " has no source");
+    (*src_off)[j + 1] += (*src_off)[j];
+  }
+  src->assign((*src_off)[new_K], 0);
+  std::vector<uint32_t> at(src_off->begin(), src_off->end() - 1);
+  for (uint64_t k = 0; k < K; ++k)  // ascending k: the sources of a new community come out ascending
+    if (map[k] >= 0) (*src)[at[map[k]]++] = static_cast<uint32_t>(k);
+}
+
+bool WritePlan(std::ostream* out, const std::vector<int32_t>& map) {
+  std::vector<uint32_t> off, src;
+  PlanSources(map, &off, &src);
+  const uint64_t new_K = off.size() - 1;
+  *out << "# " << map.size() << " " << new_K << " " << map.size() - src.size() << "\n";
+  for (uint64_t j = 0; j < new_K; ++j) {
+    *out << j << " " << off[j + 1] - off[j];
+    for (uint32_t p = off[j]; p < off[j + 1]; ++p) *out << " " << src[p];
+    *out << "\n";
+  }
+  for (uint64_t k = 0; k < map.size(); ++k)
+    if (map[k] < 0) *out << "x " << k << "\n";
+  return out->good();
+}
+
+std::vector<int32_t> ReadPlan(std::istream* in) {
+  std::string line, word;
+  uint64_t K = 0, new_K = 0, dropped = 0, no = 1;
+  {
+    if (!std::getline(*in, line)) throw std::invalid_argument("plan: line 1 is not `# K new_K dropped`");
+    std::istringstream head(line);
+    if (!(head >> word >> K >> new_K >> dropped) || word != "#" || (head >> word) || K == 0 || K > AMMSB_REDUCE_MAX_COLS)
+      throw std::invalid_argument("plan: line 1 is not `# K new_K dropped`");
+  }
+  const auto bad = [&no]() { return std::invalid_argument("plan: line " + std::to_string(no) + " does not belong to a plan over the header's communities"); };
+  std::vector<int32_t> map(K, -2);
+  uint64_t seen_new = 0, seen_drop = 0;
+  while (std::getline(*in, line)) {
+    ++no;
+    std::istringstream ls(line);
+    if (!(ls >> word)) continue;
+    std::vector<uint64_t> ks;
+    int32_t j = -1;
+    uint64_t v;
+    if (word == "x") {
+      if (!(ls >> v) || (ls >> word)) throw bad();
+      ks.push_back(v);
+      ++seen_drop;
+    } else {
+      uint64_t n = 0;
+      char* end = nullptr;
+      const unsigned long long jj = strtoull(word.c_str(), &end, 10);
+      if (*end || word[0] == '-' || jj != seen_new || !(ls >> n) || n < 1) throw bad();
+      while (ls >> v) ks.push_back(v);
+      if (!ls.eof() || ks.size() != n) throw bad();
+      j = static_cast<int32_t>(seen_new++);
+    }
+    for (uint64_t k : ks) {
+      if (k >= K || map[k] != -2) throw bad();
+      map[k] = j;
+    }
+  }
+  ++no;
+  if (seen_new != new_K || seen_drop != dropped || std::count(map.begin(), map.end(), -2)) throw bad();
+  std::vector<uint32_t> off, src;
+  PlanSources(map, &off, &src);
+  return map;
+}
+
+std::unique_ptr<Learner> Learner::Reduce(const std::vector<int32_t>& map) {
+  if (Sharded()) throw std::invalid_argument("Reduce covers one rank");
+  if (map.size() != cfg_.K)
+    throw std::invalid_argument("Reduce: a plan over " + std::to_string(map.size()) + " communities for a learner with K = " +
+                                std::to_string(cfg_.K));
+  std::vector<uint32_t> off, src;
+  PlanSources(map, &off, &src);
+  const uint32_t new_K = static_cast<uint32_t>(off.size() - 1);
+  const bool drops = src.size() != map.size(), selects = src.size() == new_K;
+  for (auto& f : futures_)
+    if (f.valid()) f.wait();
+  DrainAsync();
+  queue_.Finish();
+  std::unique_ptr<Config> cfg = CloneConfig(cfg_);
+  cfg->K = new_K;
+  std::unique_ptr<Learner> out(new Learner(*cfg, queue_));
+  out->owned_cfg_ = std::move(cfg);
+  // as Parse does: into the buffers the new learner's operators (and its captured loop) already hold
+  const clcuda::Context context = queue_.GetContext();
+  clcuda::Buffer<uint32_t> d_off(context, queue_, off.begin(), off.end()), d_src(context, queue_, src.begin(), src.end());
+  clcuda::Buffer<uint64_t> d_emptied(context, 1);
+  const uint64_t zero = 0;
+  d_emptied.Write(queue_, 1, &zero);
+  const uint64_t N = pi_->Rows(), slab = std::max<uint64_t>(1, (256ull << 20) / (sizeof(Float) * pi_->Cols()));
+  for (uint64_t lo = 0; lo < N; lo += slab) {
+    const int rc = ammsb_reduce_rows(&pi_->Get(), phi_.data(), selects ? nullptr : d_off.data(), d_src.data(), new_K, drops,
+                                     &out->pi_->Get(), out->phi_.data(), d_emptied.data(), lo, std::min(slab, N - lo),
+                                     queue_.stream());
+    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_reduce_rows: ") + ammsb_reduce_last_error());
+  }
+  int rc = ammsb_reduce_theta(theta_.data(), selects ? nullptr : d_off.data(), d_src.data(), static_cast<uint32_t>(cfg_.K), new_K,
+                              out->theta_.data(), queue_.stream());
+  if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_reduce_theta: ") + ammsb_reduce_last_error());
+  std::shared_ptr<ammsb_ctx> ctx = AcquireContext(*out->owned_cfg_, queue_);
+  ThrowIfError(ctx.get(), ammsb_beta_from_theta(ctx.get(), out->theta_.data(), out->beta_.data(), queue_.stream()),
+               "ammsb_beta_from_theta");
+  queue_.Finish();
+  uint64_t emptied = 0;
+  d_emptied.Read(queue_, 1, &emptied);
+  out->stepCount_ = stepCount_;
+  out->time_ = time_;
+  out->samplingTime_ = samplingTime_;
+  out->edges_done_ = edges_done_;
+  out->phiUpdater_.CountCalls() = phiUpdater_.CountCalls();
+  out->betaUpdater_.CountCalls() = betaUpdater_.CountCalls();
+  out->reduced_from_K_ = cfg_.K;
+  out->emptied_rows_ = emptied;
+  if (!out->cfg_.async_launch)  // the synchronous Run starts its pipeline itself only at stepCount 1
+    out->futures_[out->phase_] = std::async(std::launch::async, &Learner::DoSample, out.get(), out->samples_[out->phase_].get());
+  return out;
 }
 
 }  // namespace mcmc

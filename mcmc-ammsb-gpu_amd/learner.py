@@ -260,6 +260,7 @@ class Learner(PostFit):
         self.loop = None
         self._loop_dirty = False
         self._average = None  # ops.ChainAverage while StartAverage() is in force
+        self.reduced_from = None  # (K, emptied rows) of the learner Reduce() made this one from
         if cfg.device_sampling:
             off, tgt = dataset.training_csr()  # the host Graph's adjacency order (Graph::ExportCSR)
             # held-out links of a vertex are invalid non-link partners too (sample.cc:283-285)
@@ -1070,6 +1071,50 @@ class Learner(PostFit):
         if self._average is None or self._average.n == 0:
             raise AmmsbError("Averaged(): no sample yet (StartAverage(), then Run)")
         return AveragedModel(self)
+
+    # ------------------------------------------------------------------ fewer communities (include/ammsb_reduce.h)
+
+    def Reduce(self, plan, cfg=None):
+        """-> a new Learner over the same data set at plan.new_K communities (a _reduce.Plan, or the map[K] of one) that
+        goes on training where this one stands: pi, phi_sum and theta are this learner's under the plan -- the sources of a
+        new community added, a dropped community's mass divided out of every row -- and beta follows from theta.
+        stepCount, time, samplingTime, edges_done and the step counters of the two updaters are carried over, so the step
+        size continues.  The RNG streams, the sampler state (the pending mini-batch included) and the running mean of the
+        perplexity are the NEW learner's own fresh ones, as its constructor makes them: a reduced run is another
+        trajectory, not a replay.  cfg: the new learner's Config (its K must be plan.new_K); default a copy of this one's
+        with K replaced, alpha staying the number this Config holds (the constructor has replaced a 0 by 1/K already).
+        This learner is only drained: it can go on as if nothing had happened.  new.reduced_from = (K, rows the plan left
+        without mass, which were set uniform).  Both pi matrices are alive at once; one rank only."""
+        if not torch.cuda.is_available():
+            raise AmmsbError("no HIP device visible: reducing the model has no CPU path")
+        if self.sharded:
+            raise AmmsbError("Reduce covers one rank (world_size 1, no force_exchange)")
+        from . import _reduce
+        if not isinstance(plan, _reduce.Plan):
+            plan = _reduce.Plan(plan)
+        if plan.K != self.cfg.K:
+            raise AmmsbError("Reduce: a plan over %d communities for a learner with K = %d" % (plan.K, self.cfg.K))
+        self.drain()
+        if cfg is None:
+            import copy
+            cfg = copy.copy(self.cfg)
+            cfg.K = plan.new_K
+        elif cfg.K != plan.new_K:
+            raise AmmsbError("Reduce: cfg.K = %d, the plan leaves %d communities" % (cfg.K, plan.new_K))
+        new = Learner(cfg, self.dataset, ops=self.ops)
+        # as Parse does: into the buffers the new learner's operators (and its captured loop) already hold; new.pi is the
+        # placed pi where the placement moved it
+        reducer = self.ops.ModelReducer(new.ctx)
+        emptied = reducer.run(self.pi, self.phi, self.theta, plan, out_pi=new.pi, out_phi=new.phi, out_theta=new.theta)[3]
+        self.ops.beta_from_theta(new.ctx, new.theta, new.beta)
+        new.stepCount, new.time, new.samplingTime, new.edges_done = self.stepCount, self.time, self.samplingTime, self.edges_done
+        new.phiUpdater.count_calls = self.phiUpdater.count_calls
+        new.betaUpdater.count_calls = self.betaUpdater.count_calls
+        if new.loop is None and len(new.samples) == 2 and new.futures[new.phase] is None:
+            new._launch_sample(new.phase)   # _run starts the pipeline itself only at stepCount 1
+        self.ops.synchronize()
+        new.reduced_from = (int(self.cfg.K), int(emptied))
+        return new
 
     def PrintStats(self, out=print):
         out("TOTAL    : %.6f" % self.time)

@@ -1929,6 +1929,82 @@ class ChainAverage:
         return self.av.last_kernel_name()
 
 
+class ModelReducer:
+    """The fitted model at fewer communities (include/ammsb_reduce.h): pi, phi_sum and theta under a _reduce.Plan.  The plan
+    travels as its inverse CSR; a plan whose new communities have one source each goes as the bare source list, which is
+    the select form.  Both pi matrices are alive at once: there is no in-place form."""
+
+    def __init__(self, ctx):
+        from . import _reduce
+        self.ctx = ctx
+        self.rd = _reduce
+        self.lib = _reduce.load()
+
+    def device_plan(self, plan, select=None):
+        """-> (src_off or None, src, new_K, drops) on the device.  select: None = the select form where the plan allows it;
+        False = always the CSR (the merge form); True = refuse a plan that merges"""
+        if not isinstance(plan, self.rd.Plan):
+            plan = self.rd.Plan(plan)
+        off, src = plan.csr()
+        if select is None:
+            select = plan.selects
+        if select and not plan.selects:
+            raise AmmsbError("model reducer: the select form takes a plan that merges nothing")
+        return (None if select else self.ctx.from_numpy(off)), self.ctx.from_numpy(src), plan.new_K, plan.drops
+
+    def rows(self, pi, phi, dplan, out_pi, out_phi, emptied, first=0, count=None):
+        """rows first .. first + count under device_plan()'s tuple; emptied: a zeroed int64 [1] device tensor (needed by a
+        plan that drops).  pi and out_pi: RowPartitionedMatrix or anything with .desc"""
+        off, src, new_K, drops = dplan
+        for t, what in ((phi, "phi_sum"), (out_phi, "out_phi_sum")):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < int(pi.desc.num_rows):
+                raise AmmsbError("model reducer: %s must be a contiguous float32 vector of N elements" % what)
+        if emptied is not None and (emptied.dtype != torch.int64 or emptied.numel() < 1):
+            raise AmmsbError("model reducer: emptied must be an int64 device tensor")
+        count = int(pi.desc.num_rows) - int(first) if count is None else int(count)
+        self.rd.check(self.lib.ammsb_reduce_rows(C.byref(pi.desc), _ptr(phi), _ptr(off), _ptr(src), new_K, int(drops),
+                                                 C.byref(out_pi.desc), _ptr(out_phi), _ptr(emptied), int(first), count,
+                                                 _stream()))
+
+    def theta(self, theta, dplan, out_theta):
+        """theta [K, 2] (2K contiguous floats) -> out_theta [K', 2]"""
+        off, src, new_K, _ = dplan
+        if theta.dtype != torch.float32 or not theta.is_contiguous() or theta.numel() % 2:
+            raise AmmsbError("model reducer: theta must be a contiguous float32 [K, 2]")
+        if out_theta.dtype != torch.float32 or not out_theta.is_contiguous() or out_theta.numel() != 2 * new_K:
+            raise AmmsbError("model reducer: out_theta must be a contiguous float32 [new_K, 2]")
+        self.rd.check(self.lib.ammsb_reduce_theta(_ptr(theta), _ptr(off), _ptr(src), int(theta.numel()) // 2, new_K,
+                                                  _ptr(out_theta), _stream()))
+
+    def run(self, pi, phi, theta, plan, slab_bytes=256 << 20, out_pi=None, out_phi=None, out_theta=None, select=None):
+        """The whole model: pi in row slabs of at most slab_bytes of input, then theta.  Outputs are allocated unless
+        given (out_pi with pi's rows and plan.new_K columns).  -> (out_pi, out_phi, out_theta, emptied rows); reading the
+        count waits for the stream."""
+        if not isinstance(plan, self.rd.Plan):
+            plan = self.rd.Plan(plan)
+        if plan.K != pi.cols:
+            raise AmmsbError("model reducer: a plan over %d communities for a model of %d" % (plan.K, pi.cols))
+        if int(theta.numel()) != 2 * plan.K:
+            raise AmmsbError("model reducer: theta holds %d elements, not 2 x %d" % (theta.numel(), plan.K))
+        c = self.ctx
+        dplan = self.device_plan(plan, select)
+        if out_pi is None:
+            out_pi = RowPartitionedMatrix(c, pi.rows, plan.new_K)
+        if out_pi.rows != pi.rows or out_pi.cols != plan.new_K:
+            raise AmmsbError("model reducer: out_pi is %d x %d, not %d x %d" % (out_pi.rows, out_pi.cols, pi.rows, plan.new_K))
+        out_phi = c.empty((pi.rows,), torch.float32) if out_phi is None else out_phi
+        out_theta = c.empty((2 * plan.new_K,), torch.float32) if out_theta is None else out_theta
+        emptied = c.zeros((1,), torch.int64)
+        slab = max(1, int(slab_bytes) // (4 * pi.cols))
+        for lo in range(0, pi.rows, slab):
+            self.rows(pi, phi, dplan, out_pi, out_phi, emptied, first=lo, count=min(slab, pi.rows - lo))
+        self.theta(theta, dplan, out_theta)
+        return out_pi, out_phi, out_theta, int(emptied.item())
+
+    def kernel_name(self):
+        return self.rd.last_kernel_name()
+
+
 class GraphLoop:
     """ammsb_loop (include/ammsb.h): whole iterations replayed as captured hipGraphs over a Learner's buffers."""
 
