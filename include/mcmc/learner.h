@@ -42,7 +42,9 @@ class Learner {
   // read -- and costs a second pi in device memory; beta's mean is kept in binary64 (last thing in Step).  Both the
   // synchronous and the async loop keep it.  StartAverage() again sets the count back to 0; Parse() ends the average (the
   // checkpoint does not carry it).  Throws std::invalid_argument under Config::graph_launch and when the run is sharded.
-  void StartAverage();
+  // spread = true keeps the population variance of every entry of pi (lazily, in the same flush) and of beta (Welford, in
+  // binary64) beside the mean (include/ammsb_spread.h): a third pi in device memory.  mean and beta's mean keep their bits.
+  void StartAverage(bool spread = false);
   void StopAverage();
   uint32_t AverageSamples() const { return averaging_ ? avg_n_ : 0; }
   // the mean of beta rounded to binary32 once, and a row of the mean of pi; both flush first and throw std::runtime_error
@@ -52,6 +54,16 @@ class Learner {
   // While set, every post-fit method below reads the flushed mean of (pi, beta) instead of the last draw (and throws
   // std::runtime_error while no sample exists).  Off by default.
   void ReadAverage(bool on) { read_average_ = on; }
+  // With the spread on: beta's population variance m2 / n in binary64 and a row of pi's variance; both flush first and throw
+  // std::runtime_error without a spread or a sample.
+  std::vector<double> GetVarBeta();
+  std::vector<Float> GetVarPiRow(Vertex v);
+  // While set together with ReadAverage(true), every post-fit method reads the credible bound clamp(mean + z sd, 0, 1) of pi
+  // (z < 0: the lower bound; a fourth pi in device memory, refilled only when samples have arrived since) and the mean of
+  // beta.  ReadBound(false) frees that matrix.  The rows of a bound do not sum to 1: link scores on it are conservative
+  // scores, not probabilities.  Throws
+  // std::invalid_argument on a z that is not finite; the post-fit methods throw std::runtime_error without a spread.
+  void ReadBound(bool on, Float z = -2);
 
   // Fewer communities (include/ammsb_reduce.h; not in the reference API).  map[K]: map[k] = j sends community k to the new
   // community j in [0, K'), -1 drops it; every new community needs a source.  -> a new learner over the same data (it owns a
@@ -383,6 +395,9 @@ class Learner {
   const ammsb_rpm& PostfitPi();
   const Float* PostfitBeta();
   void FlushAverage();  // every row of mean_pi_ and mean_beta_ up to avg_n_; nothing is launched when nothing ran since
+  void FlushRows(const uint32_t* nodes, uint64_t first, uint64_t count);  // through the library the average was started with
+  void NeedSpread(const char* what) const;
+  const ammsb_rpm& BoundPi();
 
   std::unique_ptr<Config> owned_cfg_;  // a learner made by Reduce(): what cfg_ refers to (first member: destroyed last)
   uint64_t reduced_from_K_ = 0, emptied_rows_ = 0;
@@ -453,6 +468,13 @@ class Learner {
   std::unique_ptr<clcuda::Buffer<uint32_t>> avg_last_;
   std::unique_ptr<clcuda::Buffer<double>> mean_beta64_;
   std::unique_ptr<clcuda::Buffer<Float>> mean_beta_;
+  // ... and its spread: var_pi_ the population variance of the same samples, beta_m2_ Welford's sum for beta, bound_pi_ the
+  // bound matrix ReadBound asked for, filled for bound_n_ samples at bound_filled_z_
+  bool spread_ = false, read_bound_ = false;
+  Float bound_z_ = -2, bound_filled_z_ = -2;
+  uint32_t bound_n_ = 0;
+  std::unique_ptr<RowPartitionedMatrix<Float>> var_pi_, bound_pi_;
+  std::unique_ptr<clcuda::Buffer<double>> beta_m2_;
   std::unique_ptr<Sample> samples_[2];  // MCMC_SAMPLE_PARALLEL (CMakeLists.txt:42, default ON)
   std::future<Float> futures_[2];
   int phase_;

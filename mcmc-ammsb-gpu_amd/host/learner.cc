@@ -8,6 +8,7 @@
 #include "mcmc/serialize.h"
 #include "ammsb_refsample.h"
 #include "ammsb_average.h"
+#include "ammsb_spread.h"
 #include "ammsb_reduce.h"
 
 #include <hip/hip_runtime.h>
@@ -414,21 +415,34 @@ bool Learner::Sharded() const { return cfg_.exchange && cfg_.exchange->world() >
 
 void Learner::Step(Sample& s, Float weight) {
   if (Sharded()) return StepSharded(s, weight);
-  if (averaging_ && avg_n_) {  // the rows this step overwrites: their mean is brought up to the samples so far first
-    const int rc = ammsb_average_rows(&pi_->Get(), &mean_pi_->Get(), avg_last_->data(), s.dev_nodes.data(), 0, s.num_nodes,
-                                      avg_n_, queue_.stream());
-    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_rows: ") + ammsb_average_last_error());
-  }
+  // the rows this step overwrites: their mean (and variance) is brought up to the samples so far first
+  if (averaging_ && avg_n_) FlushRows(s.dev_nodes.data(), 0, s.num_nodes);
   phiUpdater_(s.dev_nodes, s.neighbor_sampler.GetData(), s.num_nodes);
   betaUpdater_(&s.dev_edges, s.num_edges, weight);
-  if (averaging_) {
+  if (averaging_ && spread_) {
+    const int rc = ammsb_spread_vector(beta_.data(), mean_beta64_->data(), beta_m2_->data(), 2 * cfg_.K, ++avg_n_, queue_.stream());
+    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_spread_vector: ") + ammsb_spread_last_error());
+  } else if (averaging_) {
     const int rc = ammsb_average_vector(beta_.data(), mean_beta64_->data(), 2 * cfg_.K, ++avg_n_, queue_.stream());
     if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_vector: ") + ammsb_average_last_error());
   }
 }
 
+// rows of the mean (with the spread on: and of the variance) to avg_n_: a node list, or first .. first + count
+void Learner::FlushRows(const uint32_t* nodes, uint64_t first, uint64_t count) {
+  if (spread_) {
+    const int rc = ammsb_spread_rows(&pi_->Get(), &mean_pi_->Get(), &var_pi_->Get(), avg_last_->data(), nodes, first, count,
+                                     avg_n_, queue_.stream());
+    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_spread_rows: ") + ammsb_spread_last_error());
+    return;
+  }
+  const int rc = ammsb_average_rows(&pi_->Get(), &mean_pi_->Get(), avg_last_->data(), nodes, first, count, avg_n_,
+                                    queue_.stream());
+  if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_rows: ") + ammsb_average_last_error());
+}
+
 // ---- the chain average (include/ammsb_average.h)
-void Learner::StartAverage() {
+void Learner::StartAverage(bool spread) {
   if (cfg_.graph_launch)
     throw std::invalid_argument("StartAverage: the chain average is kept by the eager loops, not under graph_launch");
   if (Sharded()) throw std::invalid_argument("StartAverage: the chain average covers one rank");
@@ -441,6 +455,16 @@ void Learner::StartAverage() {
     mean_beta64_.reset(new clcuda::Buffer<double>(context, 2 * cfg_.K));
     mean_beta_.reset(new clcuda::Buffer<Float>(context, 2 * cfg_.K));
   }
+  if (spread && !var_pi_) {
+    var_pi_.reset(allocFactory_->CreateMatrix(pi_->Rows(), pi_->Cols(), pi_->RowsPerBlock()));
+    beta_m2_.reset(new clcuda::Buffer<double>(queue_.GetContext(), 2 * cfg_.K));
+  } else if (!spread) {
+    var_pi_.reset();
+    beta_m2_.reset();
+  }
+  bound_pi_.reset();
+  bound_n_ = 0;
+  spread_ = spread;
   clcuda::Check(hipMemsetAsync(avg_last_->data(), 0, avg_last_->GetSize(), static_cast<hipStream_t>(queue_.stream())),
                 "hipMemsetAsync");
   avg_n_ = avg_flushed_ = 0;
@@ -452,7 +476,12 @@ void Learner::StopAverage() {
   queue_.Finish();
   averaging_ = false;
   avg_n_ = avg_flushed_ = 0;
+  spread_ = false;
+  bound_n_ = 0;
   mean_pi_.reset();
+  var_pi_.reset();
+  bound_pi_.reset();
+  beta_m2_.reset();
   avg_last_.reset();
   mean_beta64_.reset();
   mean_beta_.reset();
@@ -462,11 +491,7 @@ void Learner::FlushAverage() {
   if (!averaging_ || avg_n_ == 0) throw std::runtime_error("the chain average holds no sample (StartAverage, then Run)");
   if (avg_flushed_ == avg_n_) return;
   const uint64_t N = pi_->Rows(), slab = std::max<uint64_t>(1, (256ull << 20) / (sizeof(Float) * pi_->Cols()));
-  for (uint64_t lo = 0; lo < N; lo += slab) {
-    const int rc = ammsb_average_rows(&pi_->Get(), &mean_pi_->Get(), avg_last_->data(), nullptr, lo, std::min(slab, N - lo),
-                                      avg_n_, queue_.stream());
-    if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_rows: ") + ammsb_average_last_error());
-  }
+  for (uint64_t lo = 0; lo < N; lo += slab) FlushRows(nullptr, lo, std::min(slab, N - lo));
   const int rc = ammsb_average_round(mean_beta64_->data(), mean_beta_->data(), 2 * cfg_.K, queue_.stream());
   if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_average_round: ") + ammsb_average_last_error());
   avg_flushed_ = avg_n_;
@@ -489,6 +514,66 @@ std::vector<Float> Learner::GetMeanPiRow(Vertex v) {
   const uint32_t blk = v / mean_pi_->RowsPerBlock();
   mean_pi_->Blocks()[blk].Read(queue_, cfg_.K, row.data(), (size_t)(v % mean_pi_->RowsPerBlock()) * cfg_.K);
   return row;
+}
+
+// ---- the spread of the chain (include/ammsb_spread.h)
+void Learner::NeedSpread(const char* what) const {
+  if (!averaging_ || !spread_) throw std::runtime_error(std::string(what) + " needs the variance of the chain: StartAverage(true)");
+}
+
+void Learner::ReadBound(bool on, Float z) {
+  if (!std::isfinite(z)) throw std::invalid_argument("ReadBound: z must be finite");
+  read_bound_ = on;
+  bound_z_ = z;
+  if (!on && bound_pi_) {  // the fourth pi goes with the switch; BoundPi allocates it again when asked
+    DrainAsync();
+    queue_.Finish();
+    bound_pi_.reset();
+    bound_n_ = 0;
+  }
+}
+
+std::vector<double> Learner::GetVarBeta() {
+  NeedSpread("GetVarBeta");
+  DrainAsync();
+  queue_.Finish();
+  FlushAverage();
+  std::vector<double> v(2 * cfg_.K);
+  beta_m2_->Read(queue_, v.size(), v.data());
+  for (double& x : v) x /= static_cast<double>(avg_n_);
+  return v;
+}
+
+std::vector<Float> Learner::GetVarPiRow(Vertex v) {
+  NeedSpread("GetVarPiRow");
+  DrainAsync();
+  queue_.Finish();
+  FlushAverage();
+  std::vector<Float> row(cfg_.K);
+  const uint32_t blk = v / var_pi_->RowsPerBlock();
+  var_pi_->Blocks()[blk].Read(queue_, cfg_.K, row.data(), (size_t)(v % var_pi_->RowsPerBlock()) * cfg_.K);
+  return row;
+}
+
+// the bound matrix for the flushed state: refilled only when samples have arrived (or z has changed) since
+const ammsb_rpm& Learner::BoundPi() {
+  NeedSpread("ReadBound");
+  FlushAverage();
+  if (!bound_pi_) {
+    bound_pi_.reset(allocFactory_->CreateMatrix(pi_->Rows(), pi_->Cols(), pi_->RowsPerBlock()));
+    bound_n_ = 0;
+  }
+  if (bound_n_ != avg_n_ || bound_filled_z_ != bound_z_) {
+    const uint64_t N = pi_->Rows(), slab = std::max<uint64_t>(1, (256ull << 20) / (sizeof(Float) * pi_->Cols()));
+    for (uint64_t lo = 0; lo < N; lo += slab) {
+      const int rc = ammsb_spread_bound(&mean_pi_->Get(), &var_pi_->Get(), &bound_pi_->Get(), bound_z_, lo,
+                                        std::min(slab, N - lo), queue_.stream());
+      if (rc != AMMSB_OK) throw std::runtime_error(std::string("ammsb_spread_bound: ") + ammsb_spread_last_error());
+    }
+    bound_n_ = avg_n_;
+    bound_filled_z_ = bound_z_;
+  }
+  return bound_pi_->Get();
 }
 
 // Where pi lands in HBM (mcmc-ammsb-gpu_amd/learner.py, _place_pi): update_phi gathers 4 KiB rows of pi at random, and

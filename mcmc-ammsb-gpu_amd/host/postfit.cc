@@ -96,10 +96,12 @@ clcuda::Buffer<uint64_t> MembershipMask(const char* call, const ammsb_rpm* pi, F
 }
 }  // namespace
 
-// ---- what the analyses read: the last draw, or under ReadAverage(true) the chain average with every row flushed.  Every
+// ---- what the analyses read: the last draw, or under ReadAverage(true) the chain average with every row flushed -- with
+// ReadBound(true, z) as well, the credible bound clamp(mean + z sd, 0, 1) of pi beside the mean of beta.  Every
 // method calls these after it has drained the loop, so the flush is enqueued behind the last iteration.
 const ammsb_rpm& Learner::PostfitPi() {
   if (!read_average_) return pi_->Get();
+  if (read_bound_) return BoundPi();
   FlushAverage();
   return mean_pi_->Get();
 }

@@ -1040,19 +1040,23 @@ class Learner(PostFit):
 
     # ------------------------------------------------------------------ the chain average (include/ammsb_average.h)
 
-    def StartAverage(self):
+    def StartAverage(self, spread=False):
         """From now on keep the mean of (pi, beta) over the iterations: sample t is the state after the t-th iteration
         from here.  Costs a second pi in device memory and, per iteration, one flush of the mini-batch rows before they
-        are overwritten plus a 2K-element fold of beta.  Restarting sets the count back to 0.  Only the eager loop on one
-        rank is covered."""
+        are overwritten plus a 2K-element fold of beta.  spread=True keeps the population variance of every entry beside
+        the mean (include/ammsb_spread.h: a third pi in device memory, two more row streams per flush), which
+        Averaged() then answers for: BetaStd, MembershipSpread, Unsettled, Bound.  Restarting sets the count back to 0; a
+        restart with the other `spread` replaces the buffers.  Only the eager loop on one rank is covered."""
         if not torch.cuda.is_available():
             raise AmmsbError("no HIP device visible: the chain average has no CPU path")
         if self.loop is not None:
             raise AmmsbError("the chain average is kept by the eager loop: construct the learner with graph_launch=False")
         if self.sharded:
             raise AmmsbError("the chain average covers one rank (world_size 1, no force_exchange)")
-        if self._average is None:
-            self._average = self.ops.ChainAverage(self.ctx, self.pi, self.beta)
+        kind = self.ops.ChainSpread if spread else self.ops.ChainAverage
+        if type(self._average) is not kind:
+            self._average = None   # (the old buffers go before the new ones are allocated)
+            self._average = kind(self.ctx, self.pi, self.beta)
         else:
             self._average.reset()
 
@@ -1138,7 +1142,8 @@ class AveragedModel(PostFit):
     """The post-fit analyses over the chain average of a Learner: pi is the mean matrix, beta the mean rounded to float32,
     everything else the learner's.  drain() drains the learner and flushes every row of the mean (row slabs; nothing is
     launched when nothing ran since the last flush), so a view stays valid across further Run() calls and always answers
-    for all samples so far.  No CPU path."""
+    for all samples so far.  Where the average was started with StartAverage(spread=True) it also answers how far the
+    chain moved around that mean: BetaStd, MembershipSpread, Unsettled and Bound.  No CPU path."""
 
     def __init__(self, learner):
         L = learner
@@ -1158,3 +1163,92 @@ class AveragedModel(PostFit):
             raise AmmsbError("this view's average was stopped (StopAverage, Parse or a new learner state)")
         L.drain()
         self._avg.flush(L.pi)
+
+    # ---- the spread of the chain around the mean (include/ammsb_spread.h)
+
+    @property
+    def has_spread(self):
+        return hasattr(self._avg, "var")
+
+    def _spread(self, what):
+        if not self.has_spread:
+            raise AmmsbError("%s needs the variance of the chain: StartAverage(spread=True)" % what)
+        self.drain()
+        return self._avg
+
+    def BetaStd(self):
+        """-> [2K] float64 host array: the standard deviation of every element of the learner's beta buffer over the
+        samples, sqrt(m2 / n) of Welford's binary64 sums"""
+        sp = self._spread("BetaStd")
+        return np.sqrt(sp.beta_m2.cpu().numpy() / np.float64(sp.n))
+
+    def MembershipSpread(self, top=4, threshold=0.0, nodes=None):
+        """-> (ids, mean, sd), device tensors [n, top]: ids and mean are Memberships(top, threshold, nodes)[0:2] of the mean;
+        sd[a, j] = sqrt(var[a, ids[a, j]]) as float32, 0 in an empty slot"""
+        sp = self._spread("MembershipSpread")
+        ids, mean, _ = self.Memberships(top, threshold, nodes)
+        c = self.ctx
+        if nodes is None:
+            rows = torch.arange(self.cfg.N, device=ids.device, dtype=torch.int64)
+        else:
+            if not torch.is_tensor(nodes):
+                nodes = c.from_numpy(np.ascontiguousarray(nodes, dtype=np.uint32))
+            rows = nodes.to(torch.int64) & 0xFFFFFFFF
+        sd = torch.zeros(ids.shape, dtype=torch.float32, device=ids.device)
+        rib = sp.var.rows_in_block
+        for b, blk in enumerate(sp.var.blocks):     # a gather of n x top words per block: plumbing, not a hot path
+            here = ((rows // rib) == b)[:, None] & (ids >= 0)
+            if bool(here.any()):
+                at = ((rows % rib)[:, None] * sp.var.cols + ids.to(torch.int64).clamp(min=0))[here]
+                # (binary64's square root rounded once more is the correctly rounded binary32 one, as in the library)
+                sd[here] = blk.reshape(-1)[at].to(torch.float64).sqrt().to(torch.float32)
+        return ids, mean, sd
+
+    def Unsettled(self, top=10):
+        """-> (node ids [top] int64, total variance [top] float64), host arrays: the rows whose memberships moved most, by
+        the row sum of var descending, equal sums by node ascending"""
+        sp = self._spread("Unsettled")
+        total = sp.rowsum().cpu().numpy()
+        order = np.argsort(-total, kind="stable")[:max(0, int(top))]
+        return order.astype(np.int64), total[order]
+
+    def Bound(self, z):
+        """-> BoundedModel: every post-fit analysis over clamp(mean + z sd, 0, 1) instead of the mean; z < 0 is the lower
+        credible bound, so a membership of Bound(-2) holds at two standard deviations"""
+        self._spread("Bound")
+        return BoundedModel(self, z)
+
+
+class BoundedModel(PostFit):
+    """The post-fit analyses over a credible bound of the chain: pi[a, k] = clamp(mean[a, k] + z sd[a, k], 0, 1), a fourth
+    matrix of pi's shape allocated once per view and refilled by drain() only when samples have arrived since; beta is the
+    mean's.  Made by AveragedModel.Bound(z); stops working when the average does.  Every analysis is PostFit's, so
+    Bound(-2).CommunityQuality(0.05) scores the cover of the memberships that hold at two standard deviations.
+
+    The rows of a bound do not sum to 1.  The cover-level analyses only compare entries with a threshold and are meaningful
+    as they are; PredictLinks and LinkProbabilities multiply entries of two rows, so on a bound they return CONSERVATIVE
+    SCORES (z < 0: a floor under the link probability of the mean; z > 0: a ceiling), NOT probabilities."""
+
+    def __init__(self, averaged, z):
+        A = averaged
+        self.averaged, self._avg, self.z = A, A._avg, float(z)
+        if not np.isfinite(self.z):
+            raise AmmsbError("Bound: z must be finite, not %r" % z)
+        self.learner = A.learner
+        self.ops, self.ctx, self.cfg, self.params, self.dataset = A.ops, A.ctx, A.cfg, A.params, A.dataset
+        self.trainingSet, self.heldoutSet, self.heldoutEdges = A.trainingSet, A.heldoutSet, A.heldoutEdges
+        m = self._avg.mean
+        self.pi, self.beta = self.ops.RowPartitionedMatrix(self.ctx, m.rows, m.cols, m.rows_in_block), self._avg.beta32
+        self._filled = None   # the (chain, n) the bound matrix was last computed at: a restarted average is another chain
+        self.drain()
+
+    @property
+    def samples(self):
+        return self._avg.n
+
+    def drain(self):
+        self.averaged.drain()
+        state = (self._avg.epoch, self._avg.n)
+        if self._filled != state:
+            self._avg.bound(self.z, out=self.pi)
+            self._filled = state

@@ -1929,6 +1929,77 @@ class ChainAverage:
         return self.av.last_kernel_name()
 
 
+class ChainSpread(ChainAverage):
+    """The running mean AND population variance of (pi, beta) over the iterations since it was started
+    (include/ammsb_spread.h).  ChainAverage's interface and state, plus a third matrix of pi's geometry (var, uninitialised
+    like mean) and beta's binary64 sum of squared deviations; rows() and vector() go to libammsb_spread.so, which leaves
+    mean and beta's mean bit for bit what ChainAverage would.  bound() and rowsum() read the flushed state: call flush()
+    first."""
+
+    def __init__(self, ctx, pi, beta):
+        super().__init__(ctx, pi, beta)
+        from . import _spread
+        self.sp = _spread
+        self.splib = _spread.load()
+        self.var = RowPartitionedMatrix(ctx, pi.rows, pi.cols, pi.rows_in_block)
+        self.beta_m2 = ctx.empty((int(beta.numel()),), torch.float64)
+        self.epoch = 0     # which chain n counts: reset() starts the next one, and (epoch, n) names a state of mean and var
+
+    def reset(self):
+        super().reset()
+        self.epoch += 1
+
+    def rows(self, pi, n, nodes=None, count=None, first=0):
+        """flush the rows nodes[:count] (a contiguous int32 device tensor of uint32 ids), or first .. first + count, to n:
+        mean and var in one pass"""
+        if nodes is not None:
+            if nodes.dtype != torch.int32 or not nodes.is_contiguous():
+                raise AmmsbError("chain spread: nodes must be a contiguous int32 (uint32 bits) device tensor")
+            count = int(nodes.numel()) if count is None else int(count)
+            if count > nodes.numel():
+                raise AmmsbError("chain spread: count %d past the %d listed nodes" % (count, nodes.numel()))
+        else:
+            count = pi.rows - int(first) if count is None else int(count)
+        self.sp.check(self.splib.ammsb_spread_rows(C.byref(pi.desc), C.byref(self.mean.desc), C.byref(self.var.desc),
+                                                   _ptr(self.last), _ptr(nodes), int(first), count, int(n), _stream()))
+
+    def vector(self, x, n):
+        """fold the float32 vector x (beta) into the binary64 mean and m2 as sample n"""
+        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != self.beta64.numel():
+            raise AmmsbError("chain spread: not the learner's beta")
+        self.sp.check(self.splib.ammsb_spread_vector(_ptr(x), _ptr(self.beta64), _ptr(self.beta_m2), int(x.numel()), int(n),
+                                                     _stream()))
+
+    def bound(self, z, out=None):
+        """-> out (allocated unless given: a matrix of pi's geometry) = clamp(mean + z sd, 0, 1), in row slabs"""
+        z = float(z)
+        if not np.isfinite(z):
+            raise AmmsbError("chain spread: z must be finite, not %r" % z)
+        m = self.mean
+        if out is None:
+            out = RowPartitionedMatrix(self.ctx, m.rows, m.cols, m.rows_in_block)
+        slab = max(1, self.FLUSH_SLAB_BYTES // (4 * m.cols))
+        for lo in range(0, m.rows, slab):
+            self.sp.check(self.splib.ammsb_spread_bound(C.byref(m.desc), C.byref(self.var.desc), C.byref(out.desc), z, lo,
+                                                        min(slab, m.rows - lo), _stream()))
+        return out
+
+    def rowsum(self):
+        """-> [N] float64 device tensor: every row's total variance, in the library's one order"""
+        v = self.var
+        out = self.ctx.empty((v.rows,), torch.float64)
+        slab = max(1, self.FLUSH_SLAB_BYTES // (4 * v.cols))
+        for lo in range(0, v.rows, slab):
+            self.sp.check(self.splib.ammsb_spread_rowsum(C.byref(v.desc), C.c_void_p(out.data_ptr() + 8 * lo), lo,
+                                                         min(slab, v.rows - lo), _stream()))
+        return out
+
+    def kernel_name(self):
+        """the last kernel libammsb_spread.so launched (rows, vector, bound, rowsum).  round(), and so the end of flush(),
+        launches in libammsb_average.so, which this does not see: ChainAverage.kernel_name(self) names that one"""
+        return self.sp.last_kernel_name()
+
+
 class ModelReducer:
     """The fitted model at fewer communities (include/ammsb_reduce.h): pi, phi_sum and theta under a _reduce.Plan.  The plan
     travels as its inverse CSR; a plan whose new communities have one source each goes as the bare source list, which is
