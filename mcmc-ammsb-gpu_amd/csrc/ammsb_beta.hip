@@ -261,21 +261,20 @@ __global__ __launch_bounds__(Group<L>::BLOCK) void beta_grads_kernel(const BetaA
     const float prob_0 = w * (1.0f - pi_sum);
     probs_sum += prob_0;
     if (have[b]) {
-      // CALC_GRADS, beta.cc:161-171.  probs[j] / probs_sum with the reciprocal refined once per edge
-      // (ammsb_dev.h "exact division"): exact when every numerator is 0 or at least 2^-100 in
-      // magnitude and the divisor is in range; otherwise the plain IEEE divide.
+      // CALC_GRADS, beta.cc:161-171.  probs[j] / probs_sum with the reciprocal refined once per edge; guard and
+      // quotients: ammsb_dev.h "exact division"
       if (lo >= kProbsLo && in_range(probs_sum, kPsumLo, kPsumHi)) {
         const float rps = refined_rcp(probs_sum);
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
-          const float f = div_with_rcp(probs[j], probs_sum, rps);
+          const float f = fast_quot_rcp(probs[j], probs_sum, rps);
           acc0[j] += f * (y ? noo[j] : d0n[j]);
           acc1[j] += f * (y ? d1l[j] : noo[j]);
         }
       } else {
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
-          const float f = probs[j] / probs_sum;
+          const float f = slow_quot(probs[j], probs_sum);
           acc0[j] += f * (y ? noo[j] : d0n[j]);
           acc1[j] += f * (y ? d1l[j] : noo[j]);
         }
@@ -641,7 +640,7 @@ __device__ __forceinline__ void beta_grads_lds_body(const BetaArgs& a) {
           const f32x2 s0 = f32x2{ps0, ps0}, s1 = f32x2{ps1, ps1}, q0 = f32x2{r0, r0}, q1 = f32x2{r1, r1};
 #pragma unroll
           for (int p = 0; p < HP; ++p) {
-            const f32x2 g0 = div_exact3(pr0[p], s0, q0), g1 = div_exact3(pr1[p], s1, q1);
+            const f32x2 g0 = fast_quot(pr0[p], s0, q0), g1 = fast_quot(pr1[p], s1, q1);
             acc0[p] += g0 * sel_0(p, y0, mode);
             acc1[p] += g0 * sel_1(p, y0, mode);
             acc0[p] += g1 * sel_0(p, y1, mode);
@@ -650,10 +649,10 @@ __device__ __forceinline__ void beta_grads_lds_body(const BetaArgs& a) {
         } else {
 #pragma unroll
           for (int p = 0; p < HP; ++p) {
-            const f32x2 g0 = f32x2{pr0[p].x / ps0, pr0[p].y / ps0};
+            const f32x2 g0 = slow_quot(pr0[p], ps0);
             acc0[p] += g0 * sel_0(p, y0, mode);
             acc1[p] += g0 * sel_1(p, y0, mode);
-            const f32x2 g1 = f32x2{pr1[p].x / ps1, pr1[p].y / ps1};
+            const f32x2 g1 = slow_quot(pr1[p], ps1);
             acc0[p] += g1 * sel_0(p, y1, mode);
             acc1[p] += g1 * sel_1(p, y1, mode);
           }
@@ -687,14 +686,14 @@ __device__ __forceinline__ void beta_grads_lds_body(const BetaArgs& a) {
           const f32x2 psum2 = f32x2{probs_sum, probs_sum}, rps2 = f32x2{rps, rps};
 #pragma unroll
           for (int p = 0; p < HP; ++p) {
-            const f32x2 f = div_exact3(prr[p], psum2, rps2);
+            const f32x2 f = fast_quot(prr[p], psum2, rps2);
             acc0[p] += f * (y0 ? noo[p] : d0n[p]);
             acc1[p] += f * (y0 ? d1l[p] : noo[p]);
           }
         } else {
 #pragma unroll
           for (int p = 0; p < HP; ++p) {
-            const f32x2 f = f32x2{prr[p].x / probs_sum, prr[p].y / probs_sum};
+            const f32x2 f = slow_quot(prr[p], probs_sum);
             acc0[p] += f * (y0 ? noo[p] : d0n[p]);
             acc1[p] += f * (y0 ? d1l[p] : noo[p]);
           }
@@ -838,14 +837,14 @@ __device__ __forceinline__ void beta_grads_lds_body(const BetaArgs& a) {
       const f32x2 psum2 = f32x2{probs_sum, probs_sum}, rps2 = f32x2{rps, rps};
 #pragma unroll
       for (int p = 0; p < HP; ++p) {
-        const f32x2 f = div_exact3(prr[p], psum2, rps2);
+        const f32x2 f = fast_quot(prr[p], psum2, rps2);
         acc0[p] += f * sel_0(p, y, mode);
         acc1[p] += f * sel_1(p, y, mode);
       }
     } else {
 #pragma unroll
       for (int p = 0; p < HP; ++p) {
-        const f32x2 f = f32x2{prr[p].x / probs_sum, prr[p].y / probs_sum};
+        const f32x2 f = slow_quot(prr[p], probs_sum);
         acc0[p] += f * sel_0(p, y, mode);
         acc1[p] += f * sel_1(p, y, mode);
       }
@@ -1253,14 +1252,14 @@ __global__ __launch_bounds__(512) void beta_grads_gen_kernel(const BetaArgs a, u
         const float rps = refined_rcp(probs_sum);
 #pragma unroll
         for (int j = 0; j < CPT; ++j) {
-          const float f = div_with_rcp(probs[j], probs_sum, rps);
+          const float f = fast_quot_rcp(probs[j], probs_sum, rps);
           acc0[j] += f * (y ? noo[j] : d0n[j]);
           acc1[j] += f * (y ? d1l[j] : noo[j]);
         }
       } else {
 #pragma unroll
         for (int j = 0; j < CPT; ++j) {
-          const float f = probs[j] / probs_sum;
+          const float f = slow_quot(probs[j], probs_sum);
           acc0[j] += f * (y ? noo[j] : d0n[j]);
           acc1[j] += f * (y ? d1l[j] : noo[j]);
         }

@@ -238,6 +238,28 @@ __device__ __forceinline__ f32x2 div_exact3(f32x2 x, f32x2 d, f32x2 y) {
   return __builtin_elementwise_fma(rem, y, q0);
 }
 
+// The quotients on either side of the fast-path decision, stated once for every form of update_phi (ammsb_phi.hip) and
+// of the beta gradient (ammsb_beta.hip).  The decision stays spelled out in each kernel over the k* bounds above (as
+// functions the predicates changed the kernels' instruction streams): beta_k once per lane, phi_sum and den = pi_a *
+// phi_sum once per node, the row's smallest |numerator| and its probs_sum per row; the beta gradient needs only the last.
+// Decided fast: pr / psum (beta.cc:161-171) and (pr / psum) / den (phi.cc:259-263), the caller making RN(1 / divisor)
+// once per divisor -- exact_rcp for fast_quot, refined_rcp for fast_quot_rcp (the register kernels).
+template <class T> __device__ __forceinline__ T fast_quot(T pr, T psum, T rps) { return div_exact3(pr, psum, rps); }
+template <class T>
+__device__ __forceinline__ T fast_quot(T pr, T psum, T rps, T den, T rden) { return div_exact3(div_exact3(pr, psum, rps), den, rden); }
+__device__ __forceinline__ float fast_quot_rcp(float pr, float psum, float rps) { return div_with_rcp(pr, psum, rps); }
+__device__ __forceinline__ float fast_quot_rcp(float pr, float psum, float rps, float den, float rden) {
+  return div_with_rcp(div_with_rcp(pr, psum, rps), den, rden);
+}
+// decided slow: the same quotients by IEEE division
+__device__ __forceinline__ float slow_quot(float pr, float psum) { return pr / psum; }
+__device__ __forceinline__ f32x2 slow_quot(f32x2 pr, float psum) { return f32x2{pr.x / psum, pr.y / psum}; }
+__device__ __forceinline__ float slow_quot(float pr, float psum, float den) { return (pr / psum) / den; }
+__device__ __forceinline__ f32x2 slow_quot(f32x2 pr, float psum, f32x2 den) {
+  const f32x2 q = slow_quot(pr, psum);
+  return f32x2{q.x / den.x, q.y / den.y};
+}
+
 // ------------------------------------------------------------------------------------ cuckoo
 // Set_HasEdge, mcmc/cuckoo.cc:27-69.  Both 32-byte bins are fetched at once (two independent
 // 2 x 16 B loads each) instead of the reference's dependent second probe.

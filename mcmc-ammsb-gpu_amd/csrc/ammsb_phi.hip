@@ -56,6 +56,23 @@ extern "C" int ammsb_debug_blocks(unsigned long long* out, int n_blocks) {
 
 namespace {
 
+// ---- probs of one column pair, phi.cc:241-253: pi_a * (pi_b * f + e), bf = beta_k - EPSILON; f = bf, e = EPSILON for a
+// link (y), f = -bf, e = 1 - EPSILON for a non-link.  Two spellings, equal bit for bit (negation is exact):
+//   select: pin * (EPS - beta) + e == e - pin * (beta - EPS); with a compile-time y the sign rides on the packed add's
+//           source modifier;
+//   sign:   e - t == e + t * -1, so with sg = y ? 1 : -1 one straight-line statement serves rows of either kind.
+// The packed forms call these; the one-column forms (register, wide, gen) spell the same statements out, and every form
+// keeps its SGLD step (phi.cc:265-274): through helpers their instruction streams changed.
+__device__ __forceinline__ f32x2 probs_select(f32x2 pin, f32x2 bf, float e, bool y, f32x2 pi_a) {
+  const f32x2 tt0 = pin * bf;
+  const f32x2 tt = y ? tt0 + e : e - tt0;
+  return pi_a * tt;
+}
+__device__ __forceinline__ f32x2 probs_sign(f32x2 pin, f32x2 bf, float sg, float e, f32x2 pi_a) {
+  const f32x2 tt = (pin * bf) * sg + e;
+  return pi_a * tt;
+}
+
 struct PhiArgs {
   const float* beta;
   ammsb_rpm pi;
@@ -127,7 +144,7 @@ __global__ __launch_bounds__(Group<L>::BLOCK) void update_phi_kernel(const PhiAr
 
   // per-lane constants: f = beta_k - EPSILON for a link, its exact negation for a non-link
   float bf[KPT];
-  bool beta_safe = true;  // every beta_k this lane owns lies in [EPSILON, 1 - 2^-20] (exact-division fast path)
+  bool beta_safe = true;  // the lane's share of the fast-path guards (ammsb_dev.h "exact division")
 #pragma unroll
   for (int j = 0; j < KPT; ++j) {
     const float b = a.beta[2 * ccol(j) + 1];
@@ -189,8 +206,7 @@ __global__ __launch_bounds__(Group<L>::BLOCK) void update_phi_kernel(const PhiAr
       const float e = y ? EPS : 1.0f - EPS;
       float partial = 0.0f;
       float lo = 1.0f;  // smallest |probs| of this lane (columns that exist)
-      // phi.cc:241-253; pin[] is overwritten with probs[].  pin * (EPS - beta) + e == e - pin * (beta - EPS)
-      // bit for bit, so the non-link case subtracts instead of selecting a negated factor.
+      // phi.cc:241-253; pin[] is overwritten with probs[] (the select spelling of probs_select, spelled out)
       if (y) {
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
@@ -217,15 +233,13 @@ __global__ __launch_bounds__(Group<L>::BLOCK) void update_phi_kernel(const PhiAr
         const float rps = refined_rcp(probs_sum);
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
-          float qv = div_with_rcp(pin[j], probs_sum, rps);
-          qv = div_with_rcp(qv, pi_a[j] * phi_sum, rden[j]);
+          const float qv = fast_quot_rcp(pin[j], probs_sum, rps, pi_a[j] * phi_sum, rden[j]);
           grads[j] += qv - inv_phi_sum;
         }
       } else {
 #pragma unroll
         for (int j = 0; j < KPT; ++j) {
-          float qv = pin[j] / probs_sum;
-          qv = qv / (pi_a[j] * phi_sum);
+          const float qv = slow_quot(pin[j], probs_sum, pi_a[j] * phi_sum);
           grads[j] += qv - inv_phi_sum;
         }
       }
@@ -274,8 +288,7 @@ __global__ __launch_bounds__(Group<L>::BLOCK) void update_phi_kernel(const PhiAr
               float qv[4];
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
-                qv[r] = div_with_rcp(pin[r][j], psum[r], rps[r]);
-                qv[r] = div_with_rcp(qv[r], pi_a[j] * phi_sum, rden[j]);
+                qv[r] = fast_quot_rcp(pin[r][j], psum[r], rps[r], pi_a[j] * phi_sum, rden[j]);
               }
 #pragma unroll
               for (int r = 0; r < 4; ++r) grads[j] += qv[r] - inv_phi_sum;
@@ -287,15 +300,13 @@ __global__ __launch_bounds__(Group<L>::BLOCK) void update_phi_kernel(const PhiAr
                 const float rps = refined_rcp(psum[r]);
 #pragma unroll
                 for (int j = 0; j < KPT; ++j) {
-                  float qv = div_with_rcp(pin[r][j], psum[r], rps);
-                  qv = div_with_rcp(qv, pi_a[j] * phi_sum, rden[j]);
+                  const float qv = fast_quot_rcp(pin[r][j], psum[r], rps, pi_a[j] * phi_sum, rden[j]);
                   grads[j] += qv - inv_phi_sum;
                 }
               } else {
 #pragma unroll
                 for (int j = 0; j < KPT; ++j) {
-                  float qv = pin[r][j] / psum[r];
-                  qv = qv / (pi_a[j] * phi_sum);
+                  const float qv = slow_quot(pin[r][j], psum[r], pi_a[j] * phi_sum);
                   grads[j] += qv - inv_phi_sum;
                 }
               }
@@ -613,17 +624,14 @@ __global__ __launch_bounds__(64 * W * NB) __attribute__((amdgpu_waves_per_eu(KPT
       y = __builtin_amdgcn_readfirstlane((int)y) != 0;
       const float e = y ? EPS : 1.0f - EPS;
 
-      // pass 1 (phi.cc:241-253): probs[] in place of the row, lane partial in ascending column order.
-      // pin * (EPS - beta) + e == e - pin * (beta - EPS) bit for bit; the two wave-uniform cases are separate
-      // code so that the sign rides on the packed add's source modifier.
+      // pass 1 (probs_select): probs[] in place of the row, lane partial in ascending column order; the two
+      // wave-uniform cases are separate code so that the sign rides on the packed add's source modifier
       float partial = 0.0f, lo = 1.0f;
       auto pass1 = [&](auto link) {
 #pragma unroll
         for (int p = 0; p < HP; ++p) {
           const f32x2 pin = f32x2{row[ln + 128 * p], row[ln + 128 * p + 64]};
-          const f32x2 tt0 = pin * bf[p];
-          const f32x2 tt = decltype(link)::value ? tt0 + e : e - tt0;
-          const f32x2 pr = pi_a[p] * tt;
+          const f32x2 pr = probs_select(pin, bf[p], e, decltype(link)::value, pi_a[p]);
           row[ln + 128 * p] = pr.x;
           row[ln + 128 * p + 64] = pr.y;
           VLn::chain(partial, pr.x);
@@ -644,19 +652,15 @@ __global__ __launch_bounds__(64 * W * NB) __attribute__((amdgpu_waves_per_eu(KPT
 #pragma unroll
         for (int p = 0; p < HP; ++p) {
           const f32x2 pr = f32x2{row[ln + 128 * p], row[ln + 128 * p + 64]};
-          f32x2 qv = div_exact3(pr, psum2, rps2);
-          qv = div_exact3(qv, pi_a[p] * ps, rden[p]);
+          const f32x2 qv = fast_quot(pr, psum2, rps2, pi_a[p] * ps, rden[p]);
           grads[p] += qv - inv_phi_sum;
         }
       } else {
 #pragma unroll
         for (int p = 0; p < HP; ++p) {
-          const f32x2 den = pi_a[p] * phi_sum;
-          float q0 = row[ln + 128 * p] / probs_sum;
-          float q1 = row[ln + 128 * p + 64] / probs_sum;
-          q0 = q0 / den.x;
-          q1 = q1 / den.y;
-          grads[p] += f32x2{q0 - inv_phi_sum, q1 - inv_phi_sum};
+          const f32x2 pr = f32x2{row[ln + 128 * p], row[ln + 128 * p + 64]};
+          const f32x2 qv = slow_quot(pr, probs_sum, pi_a[p] * phi_sum);
+          grads[p] += f32x2{qv.x - inv_phi_sum, qv.y - inv_phi_sum};
         }
       }
     }
@@ -832,9 +836,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void up
 #pragma unroll
         for (int p = 0; p < HP; ++p) {
           const f32x2 pin = f32x2{row[ln + 128 * p], row[ln + 128 * p + 64]};
-          const f32x2 tt0 = pin * bf[p];
-          const f32x2 tt = decltype(link)::value ? tt0 + e : e - tt0;
-          const f32x2 pr = pi_a[p] * tt;
+          const f32x2 pr = probs_select(pin, bf[p], e, decltype(link)::value, pi_a[p]);
           row[ln + 128 * p] = pr.x;
           row[ln + 128 * p + 64] = pr.y;
           VLn::chain(partial, pr.x);
@@ -855,19 +857,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void up
 #pragma unroll
         for (int p = 0; p < HP; ++p) {
           const f32x2 pr = f32x2{row[ln + 128 * p], row[ln + 128 * p + 64]};
-          f32x2 qv = div_exact3(pr, psum2, rps2);
-          qv = div_exact3(qv, pi_a[p] * ps, rden[p]);
+          const f32x2 qv = fast_quot(pr, psum2, rps2, pi_a[p] * ps, rden[p]);
           grads[p] += qv - inv_phi_sum;
         }
       } else {
 #pragma unroll
         for (int p = 0; p < HP; ++p) {
-          const f32x2 den = pi_a[p] * phi_sum;
-          float q0 = row[ln + 128 * p] / probs_sum;
-          float q1 = row[ln + 128 * p + 64] / probs_sum;
-          q0 = q0 / den.x;
-          q1 = q1 / den.y;
-          grads[p] += f32x2{q0 - inv_phi_sum, q1 - inv_phi_sum};
+          const f32x2 pr = f32x2{row[ln + 128 * p], row[ln + 128 * p + 64]};
+          const f32x2 qv = slow_quot(pr, probs_sum, pi_a[p] * phi_sum);
+          grads[p] += f32x2{qv.x - inv_phi_sum, qv.y - inv_phi_sum};
         }
       }
       slot = slot == 2 ? 0u : slot + 1u;
@@ -1084,9 +1082,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT == 4 ? 4
       for (int r = 0; r < U; ++r) {
         const bool y = (__builtin_amdgcn_readfirstlane(s_nb[q + r]) >> 31) != 0;
         ee[r] = y ? EPS : 1.0f - EPS;
-        // pin * (EPS - beta) + e == e - pin * (beta - EPS) == e + (-(pin * (beta - EPS))): the negation is exact, so
-        // multiplying by -1 for a non-link and adding gives the single-row kernel's value bit for bit
-        sg[r] = y ? 1.0f : -1.0f;
+        sg[r] = y ? 1.0f : -1.0f;  // (probs_sign)
         part[r] = 0.0f;
         lo[r] = 1.0f;
       }
@@ -1097,8 +1093,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT == 4 ? 4
 #pragma unroll
         for (int r = 0; r < U; ++r) {
           const f32x2 pin = f32x2{row[r][ln + 128 * p], row[r][ln + 128 * p + 64]};
-          const f32x2 tt = (pin * bf[p]) * sg[r] + ee[r];
-          const f32x2 pr = pi_a[p] * tt;
+          const f32x2 pr = probs_sign(pin, bf[p], sg[r], ee[r], pi_a[p]);
           if constexpr (REGP) {
             prr[r][p] = pr;
           } else {
@@ -1138,7 +1133,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT == 4 ? 4
             f32x2 pr;
             if constexpr (REGP) pr = prr[r][p];
             else pr = f32x2{row[r][ln + 128 * p], row[r][ln + 128 * p + 64]};
-            v[r] = div_exact3(div_exact3(pr, s2[r], r2[r]), den, rden[p]);
+            v[r] = fast_quot(pr, s2[r], r2[r], den, rden[p]);
           }
 #pragma unroll
           for (int r = 0; r < U; ++r) grads[p] += v[r] - inv_phi_sum;
@@ -1157,25 +1152,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT == 4 ? 4
               f32x2 pr;
               if constexpr (REGP) pr = prr[r][p];
               else pr = f32x2{row[r][ln + 128 * p], row[r][ln + 128 * p + 64]};
-              f32x2 qv = div_exact3(pr, psum2, rps2);
-              qv = div_exact3(qv, pi_a[p] * ps, rden[p]);
+              const f32x2 qv = fast_quot(pr, psum2, rps2, pi_a[p] * ps, rden[p]);
               grads[p] += qv - inv_phi_sum;
             }
           } else {
 #pragma unroll
             for (int p = 0; p < HP; ++p) {
-              const f32x2 den = pi_a[p] * phi_sum;
-              float v0, v1;
-              if constexpr (REGP) {
-                v0 = prr[r][p].x / probs_sum;
-                v1 = prr[r][p].y / probs_sum;
-              } else {
-                v0 = row[r][ln + 128 * p] / probs_sum;
-                v1 = row[r][ln + 128 * p + 64] / probs_sum;
-              }
-              v0 = v0 / den.x;
-              v1 = v1 / den.y;
-              grads[p] += f32x2{v0 - inv_phi_sum, v1 - inv_phi_sum};
+              f32x2 pr;
+              if constexpr (REGP) pr = prr[r][p];
+              else pr = f32x2{row[r][ln + 128 * p], row[r][ln + 128 * p + 64]};
+              const f32x2 qv = slow_quot(pr, probs_sum, pi_a[p] * phi_sum);
+              grads[p] += f32x2{qv.x - inv_phi_sum, qv.y - inv_phi_sum};
             }
           }
         }
@@ -1391,7 +1378,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT <= 8 ? 4
       for (int r = 0; r < U; ++r) {
         const bool y = (s_nb[q + r] >> 31) != 0;  // this half's flag
         ee[r] = y ? EPS : 1.0f - EPS;
-        sg[r] = y ? 1.0f : -1.0f;  // e - pin (beta - EPS) == e + (-(pin (beta - EPS))): the negation is exact
+        sg[r] = y ? 1.0f : -1.0f;  // (probs_sign)
         lo[r] = 1.0f;
 #pragma unroll
         for (int v = 0; v < NS; ++v) part[r][v] = 0.0f;
@@ -1402,8 +1389,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT <= 8 ? 4
 #pragma unroll
         for (int r = 0; r < U; ++r) {
           const f32x2 pin = f32x2{row[r][lds_col(2 * p)], row[r][lds_col(2 * p + 1)]};
-          const f32x2 tt = (pin * bf[p]) * sg[r] + ee[r];
-          const f32x2 pr = pi_a[p] * tt;
+          const f32x2 pr = probs_sign(pin, bf[p], sg[r], ee[r], pi_a[p]);
           prr[r][p] = pr;
           part[r][0] += pr.x;       // VL = 32: one chain over j = 2p, 2p + 1; VL = 64: work-item l takes the even j,
           part[r][NS - 1] += pr.y;  // work-item l + 32 the odd ones
@@ -1434,7 +1420,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT <= 8 ? 4
           const f32x2 den = pi_a[p] * ps;
           f32x2 v[U];
 #pragma unroll
-          for (int r = 0; r < U; ++r) v[r] = div_exact3(div_exact3(prr[r][p], s2[r], r2[r]), den, rden[p]);
+          for (int r = 0; r < U; ++r) v[r] = fast_quot(prr[r][p], s2[r], r2[r], den, rden[p]);
 #pragma unroll
           for (int r = 0; r < U; ++r) grads[p] += v[r] - inv_phi_sum;
         }
@@ -1447,18 +1433,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(KPT <= 8 ? 4
             const f32x2 psum2 = f32x2{probs_sum, probs_sum}, rps2 = f32x2{rps, rps};
 #pragma unroll
             for (int p = 0; p < HP; ++p) {
-              f32x2 qv = div_exact3(prr[r][p], psum2, rps2);
-              qv = div_exact3(qv, pi_a[p] * phi_sum, rden[p]);
+              const f32x2 qv = fast_quot(prr[r][p], psum2, rps2, pi_a[p] * phi_sum, rden[p]);
               grads[p] += qv - inv_phi_sum;
             }
           } else {
 #pragma unroll
             for (int p = 0; p < HP; ++p) {
-              const f32x2 den = pi_a[p] * phi_sum;
-              float v0 = prr[r][p].x / probs_sum, v1 = prr[r][p].y / probs_sum;
-              v0 = v0 / den.x;
-              v1 = v1 / den.y;
-              grads[p] += f32x2{v0 - inv_phi_sum, v1 - inv_phi_sum};
+              const f32x2 qv = slow_quot(prr[r][p], probs_sum, pi_a[p] * phi_sum);
+              grads[p] += f32x2{qv.x - inv_phi_sum, qv.y - inv_phi_sum};
             }
           }
         }
@@ -1606,15 +1588,13 @@ __global__ __launch_bounds__(64 * (RW + 1)) void update_phi_wide_kernel(const Ph
           const float rps = exact_rcp(probs_sum);
 #pragma unroll
           for (int j = 0; j < KPT; ++j) {
-            float qv = div_exact3(pr[j], probs_sum, rps);
-            qv = div_exact3(qv, pi_a[j] * phi_sum, rden[j]);
+            const float qv = fast_quot(pr[j], probs_sum, rps, pi_a[j] * phi_sum, rden[j]);
             tq[ln + 64 * j] = qv - inv_phi_sum;
           }
         } else {
 #pragma unroll
           for (int j = 0; j < KPT; ++j) {
-            float qv = pr[j] / probs_sum;
-            qv = qv / (pi_a[j] * phi_sum);
+            const float qv = slow_quot(pr[j], probs_sum, pi_a[j] * phi_sum);
             tq[ln + 64 * j] = qv - inv_phi_sum;
           }
         }
@@ -1933,7 +1913,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void up
       for (int r = 0; r < U; ++r) {
         const bool y = (__builtin_amdgcn_readfirstlane(s_nb[q + r]) >> 31) != 0;
         ee[r] = y ? EPS : 1.0f - EPS;
-        sg[r] = y ? 1.0f : -1.0f;  // e - pin (beta - EPS) == e + (-(pin (beta - EPS))): the negation is exact
+        sg[r] = y ? 1.0f : -1.0f;  // (probs_sign)
         part[r] = 0.0f;
         lo[r] = 1.0f;
       }
@@ -1944,8 +1924,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void up
 #pragma unroll
         for (int r = 0; r < U; ++r) {
           const f32x2 pin = f32x2{row[r][tid + 128 * p], row[r][tid + 128 * p + 64]};
-          const f32x2 tt = (pin * bf[p]) * sg[r] + ee[r];
-          const f32x2 pr = pi_a[p] * tt;
+          const f32x2 pr = probs_sign(pin, bf[p], sg[r], ee[r], pi_a[p]);
           prr[r][p] = pr;
           vx[r] = pr.x;
           vy[r] = pr.y;
@@ -1976,7 +1955,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void up
           const f32x2 den = pi_a[p] * ps;
           f32x2 v[U];
 #pragma unroll
-          for (int r = 0; r < U; ++r) v[r] = div_exact3(div_exact3(prr[r][p], s2[r], r2[r]), den, rden[p]);
+          for (int r = 0; r < U; ++r) v[r] = fast_quot(prr[r][p], s2[r], r2[r], den, rden[p]);
 #pragma unroll
           for (int r = 0; r < U; ++r) grads[p] += v[r] - inv_phi_sum;
         }
@@ -1989,18 +1968,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void up
             const f32x2 psum2 = f32x2{probs_sum, probs_sum}, rps2 = f32x2{rps, rps};
 #pragma unroll
             for (int p = 0; p < HP; ++p) {
-              f32x2 qv = div_exact3(prr[r][p], psum2, rps2);
-              qv = div_exact3(qv, pi_a[p] * phi_sum, rden[p]);
+              const f32x2 qv = fast_quot(prr[r][p], psum2, rps2, pi_a[p] * phi_sum, rden[p]);
               grads[p] += qv - inv_phi_sum;
             }
           } else {
 #pragma unroll
             for (int p = 0; p < HP; ++p) {
-              const f32x2 den = pi_a[p] * phi_sum;
-              float v0 = prr[r][p].x / probs_sum, v1 = prr[r][p].y / probs_sum;
-              v0 = v0 / den.x;
-              v1 = v1 / den.y;
-              grads[p] += f32x2{v0 - inv_phi_sum, v1 - inv_phi_sum};
+              const f32x2 qv = slow_quot(prr[r][p], probs_sum, pi_a[p] * phi_sum);
+              grads[p] += f32x2{qv.x - inv_phi_sum, qv.y - inv_phi_sum};
             }
           }
         }
@@ -2367,15 +2342,13 @@ __global__ __launch_bounds__(512) void update_phi_gen_kernel(const PhiArgs a, ui
           const float rps = exact_rcp(probs_sum);
 #pragma unroll
           for (int j = 0; j < CPT; ++j) {
-            float qv = div_exact3(pr[r][j], probs_sum, rps);
-            qv = div_exact3(qv, pi_a[j] * phi_sum, rden[j]);
+            const float qv = fast_quot(pr[r][j], probs_sum, rps, pi_a[j] * phi_sum, rden[j]);
             grads[j] += qv - inv_phi_sum;
           }
         } else {
 #pragma unroll
           for (int j = 0; j < CPT; ++j) {
-            float qv = pr[r][j] / probs_sum;
-            qv = qv / (pi_a[j] * phi_sum);
+            const float qv = slow_quot(pr[r][j], probs_sum, pi_a[j] * phi_sum);
             grads[j] += qv - inv_phi_sum;
           }
         }

@@ -1,4 +1,5 @@
-// What the range guards of the exact-division fast path protect (ammsb_dev.h "exact division"): reads binary32 (x, d)
+// What the range guards of the exact-division fast path protect (ammsb_dev.h "exact division", where the bounds and the
+// fast / slow quotients of every update_phi and beta-gradient form are stated once): reads binary32 (x, d)
 // operand pairs from a file and counts the quotients that the two unguarded tails get wrong against IEEE `x / d`:
 //   three instructions (Markstein), y = RN(1 / d):   q0 = x*y; rem = fma(-d, q0, x); q = fma(rem, y, q0)
 //   five instructions, from a reciprocal seed within 1 ulp of RN(1 / d), refined once (as div_check.c does):

@@ -1,5 +1,6 @@
 """Inputs that put update_phi and the beta gradient on BOTH sides of the exact-division branch (ammsb_dev.h "exact
-division"), a host statement of that branch's guards, and the coverage conditions the inputs must meet.
+division", the one home of the guards' bounds and of the quotients on either side; every kernel form calls them from
+its own branch), a host statement of that branch's guards, and the coverage conditions the inputs must meet.
 
 Plain numpy: imports without torch and without a GPU.  The oracle module (oracle_lib) is handed in where the reference's
 own generators are needed (host_state); nothing here touches a device.
